@@ -6,11 +6,15 @@ shac.py:411 do, minus the actor network).  N GPUs = N processes (torch.distribut
 shard of environments; no collective touches the data path (the all_reduce below only combines timings).
 
 The timed submission is a HIP-graph replay of that rollout (captured once through DFlexEnv.step with
-diffrl_amd/graph.py, checked bit for bit against the eager loop; every replay re-executes all launches); the same
-rollouts driven step by step from Python are reported as `eager_env_steps_per_s` (`--eager` times those instead).
+diffrl_amd/graph.py; every replay re-executes all launches); `--eager` times the rollouts driven step by step from Python
+instead.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel (the adjoint kernel), `cpu_baseline`
-times the scalar CPU oracle on a bounded sample of the same workload on the box's host cores.
+A plain run sets up, warms up (`--warmup` replays), times `--steps` replays and prints ONE JSON line (rank 0) with the
+headline (`value`, `ms_per_step`).  `--full` adds what takes runs of its own: the graph replay checked bit for bit against the
+eager loop, the eager loop's rate (`eager_env_steps_per_s`), the forward-only no-grad rate, `roofline` for the dominant kernel
+(kernel times by HIP events), the other BASELINE.json configurations and `cpu_baseline` (the scalar CPU oracle on a bounded
+sample of the same workload on the host cores).  `--dump-outputs DIR` writes what the last timed step returned to its caller
+(the gradient of the loss with respect to the actions, and the loss) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -41,7 +45,8 @@ def make_env(name, n, device):
 
 
 def rollout(env, actions):
-    """one SHAC-style trajectory: H x env.step on fresh environments, loss = -sum of rewards, one backward"""
+    """one SHAC-style trajectory: H x env.step on fresh environments, loss = -sum of rewards, one backward; returns the
+    actions' gradient (the loss is left in rollout.loss)"""
     env.clear_grad()
     env.reset()
     env.initialize_trajectory()
@@ -52,6 +57,7 @@ def rollout(env, actions):
         rews.append(rew)
     loss = reward_loss(rews)
     loss.backward()
+    rollout.loss = loss.detach()
     return acts.grad
 
 
@@ -346,6 +352,28 @@ def csrc_hash():
     return h.hexdigest()[:12]
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all arrays of all ranks together
+
+
+def dump_outputs(d, arrays, rank=0, world=1):
+    """--dump-outputs: each array as d/<name>.npy (float32 / float64; <name>_rank<r>.npy with several ranks).  An array over its
+    share of DUMP_MAX_BYTES is replaced by a fixed, seeded sample of its flattened elements (the same indices on every run),
+    with the flat indices it kept in <name>_index.npy (float64, exact)"""
+    os.makedirs(d, exist_ok=True)
+    budget = DUMP_MAX_BYTES // (max(len(arrays), 1) * world)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        if x.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64 if x.dtype.itemsize > 4 else np.float32)
+        if x.nbytes > budget:
+            k = budget // (x.itemsize + 8)   # (the sample and its float64 index share the budget)
+            idx = np.sort(np.random.default_rng(0).choice(x.size, size=k, replace=False))
+            np.save(os.path.join(d, name + "_index" + suffix + ".npy"), idx.astype(np.float64))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(d, name + suffix + ".npy"), x)
+
+
 MAX_LINE_BYTES = 4096   # the driver reads the LAST stdout line out of a bounded tail: round 5's 21 KB line was not parsed
 
 
@@ -439,10 +467,16 @@ def parse_args(argv=None):
     ap.add_argument("--envs-per-gpu", type=int, default=1024)
     ap.add_argument("--horizon", type=int, default=32)
     ap.add_argument("--mm-freq", type=int, default=0, help="MM_caching_frequency (0: the examples/cfg/shac value)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: graph replay against the eager loop, eager and "
+                         "forward-only rates, roofline (kernel times), other configurations, CPU baseline; a plain run times the "
+                         "headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (actions' gradient, loss) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the short measurements of the other BASELINE.json configurations (Humanoid 1024 x 32, SNUHumanoid "
-                         "512 x 32, Ant with MM_caching_frequency 1) that the default single-GPU Ant run appends as `other_configs`")
+                         "512 x 32, Ant with MM_caching_frequency 1) that a --full single-GPU Ant run appends as `other_configs`")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the informational legs (Python-driven eager loop, forward-only no-grad loop): under rocprofv3 every "
                          "launch of a kernel is then a launch of the timed rollout or of the kernel timing (tools/profile.sh)")
@@ -484,8 +518,8 @@ def launch_ranks(a, argv):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     a = parse_args(argv)
-    if a.gpus < 1 or a.oversubscribe < 1:
-        sys.stderr.write("bench.py: --gpus and --oversubscribe must be >= 1\n")
+    if a.gpus < 1 or a.oversubscribe < 1 or a.steps < 1:
+        sys.stderr.write("bench.py: --gpus, --oversubscribe and --steps must be >= 1\n")
         return 2
     under_launcher = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if not under_launcher and (a.gpus > 1 or a.oversubscribe > 1 or a.launcher or a.dry_run):
@@ -571,7 +605,7 @@ def main(argv=None):
         # (diffrl_amd/graph.py).  Every replay re-executes all 64 launches on the same inputs.
         try:
             from diffrl_amd.graph import GraphedRollout
-            g_eager = rollout(env, actions).clone()
+            g_eager = rollout(env, actions).clone() if a.full else None
             acts = actions.detach().clone().requires_grad_(True)
 
             def body(e):
@@ -582,9 +616,10 @@ def main(argv=None):
             env.clear_grad()
             env.reset()
             roll = GraphedRollout(env, body, leaves=[acts], carry_state=False)
-            roll.replay()
-            torch.cuda.synchronize()
-            assert torch.equal(acts.grad, g_eager), "graph replay and eager rollout disagree"
+            if a.full:
+                roll.replay()
+                torch.cuda.synchronize()
+                assert torch.equal(acts.grad, g_eager), "graph replay and eager rollout disagree"
             submission = "one HIP graph per rollout: the %d forward + %d adjoint launches captured through DFlexEnv.step" % (H, H)
         except Exception as ex:  # capture unsupported on this stack: measure the eager loop instead, and say so LOUDLY
             roll = None
@@ -594,9 +629,11 @@ def main(argv=None):
 
     def one():
         if roll is not None:
-            roll.replay()
+            one.loss = roll.replay()
             return acts.grad
-        return rollout(env, actions)
+        g = rollout(env, actions)
+        one.loss = rollout.loss
+        return g
 
     for _ in range(a.warmup):
         one()
@@ -621,6 +658,9 @@ def main(argv=None):
     gc.enable()
     per_step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(a.steps)) if marks else []
     assert torch.isfinite(grad).all()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"actions_grad": grad.detach().float().cpu().numpy(),
+                                      "loss": one.loss.detach().float().cpu().numpy()}, rank, world)
     el_rank = el_own
     el = sharding.max_over_ranks(el, red_dev)
     total_env_steps = a.steps * world * n * H
@@ -632,7 +672,7 @@ def main(argv=None):
     eager_value = None
     # (the informational legs below are rank 0's alone: with several ranks they are skipped, so that no rank waits more than the
     # second or two of the kernel timings at the closing barrier)
-    if roll is not None and rank == 0 and not a.no_extras and world == 1:
+    if a.full and roll is not None and rank == 0 and not a.no_extras and world == 1:
         # the same rollouts driven step by step from Python (what a caller that does not capture gets)
         env2 = make_env(a.env, n, str(device))
         for _ in range(2):
@@ -646,8 +686,6 @@ def main(argv=None):
         del env2
 
     if rank == 0:
-        rf = roofline_record(env, a.env, n, H, mm, device, 50)
-        eng = env.model.engine()
         out = {
             "metric": "fwd+adjoint env-steps/sec", "value": value, "unit": "env-steps/s", "n_gpus": a.gpus,
             "rccl_ranks": rccl_ranks, "oversubscribed": over,
@@ -666,13 +704,14 @@ def main(argv=None):
                        "substeps": env.sim_substeps,
                        "mm_freq": mm, "sharding": "envs by index, no collective", "submission": submission,
                        "submission_fallback": fallback},
-            "eager_env_steps_per_s": eager_value,
-            "roofline": rf,
-            "fp32_valu_frac_est": rf.get("fp32_valu_frac_est"),
         }
-        rf["alg_frac_step"] = ALG_BYTES[a.env] * (value / world) / (HBM_PEAK_GBS * 1e9)   # per GPU: whole env-step bytes x rate / 8 TB/s
+        if a.full:
+            rf = roofline_record(env, a.env, n, H, mm, device, 50)
+            eng = env.model.engine()
+            out.update({"eager_env_steps_per_s": eager_value, "roofline": rf, "fp32_valu_frac_est": rf.get("fp32_valu_frac_est")})
+            rf["alg_frac_step"] = ALG_BYTES[a.env] * (value / world) / (HBM_PEAK_GBS * 1e9)   # per GPU: whole env-step bytes x rate / 8 TB/s
         # forward-only serving path (dflex.config.no_grad: no checkpoint traffic), SURVEY.md 8(f).4 -- informational
-        if not a.no_extras and world == 1:
+        if a.full and not a.no_extras and world == 1:
             with torch.no_grad():
                 spec = env._spec()
                 q, qd = env.state.joint_q.detach().clone(), env.state.joint_qd.detach().clone()
@@ -688,7 +727,7 @@ def main(argv=None):
             out["backend"] = "gloo"
             out["note"] = ("%d ranks share each GPU (--oversubscribe): the multi-rank launcher / sharding / timing path executed against "
                            "real kernels, NOT a multi-GPU figure -- the ranks' launches time-slice one device" % a.oversubscribe)
-        if not a.no_other_configs and world == 1 and a.env == "ant" and not a.eager:
+        if a.full and not a.no_other_configs and world == 1 and a.env == "ant" and not a.eager:
             # BASELINE.json configs[2], configs[3] and the MM_caching_frequency = 1 variant of configs[1] (SURVEY.md 8(d):
             # "also report 1"), each a few seconds: driver-visible numbers next to the headline
             del env, roll
@@ -703,7 +742,7 @@ def main(argv=None):
                                     # the headline workload on the GENERIC kernels (run-time layout: what a user model that
                                     # matches no specialised kernel set gets; tools/gen_static_layouts.py adds a set)
                                     measure_other_config("ant", n, H, MM_FREQ["ant"], device, generic=True)]
-        if not a.no_cpu_baseline and world == 1:   # reported at N = 1 only (the host cores are the same for every N)
+        if a.full and not a.no_cpu_baseline and world == 1:   # reported at N = 1 only (the host cores are the same for every N)
             out["cpu_baseline"] = cpu_baseline(a.env)
         emit(out)
     if dist:

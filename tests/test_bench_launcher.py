@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,6 +101,41 @@ def test_printed_line_is_compact_and_complete(ranks):
     assert abs(j["value"] / full["value"] - 1) < 1e-4   # (5 significant digits in the printed line, every bit in the full record)
 
 
+def test_full_is_off_by_default():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse_args(["--gpus", "1", "--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_float_arrays_under_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files, all of them within DUMP_MAX_BYTES; an array over its share is replaced by
+    the same seeded sample on every run, with the flat indices it kept"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 16)
+    big = np.random.default_rng(3).standard_normal((40, 1000)).astype(np.float32)
+    files = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        bench.dump_outputs(str(d), {"actions_grad": big, "loss": np.float32(-2.5), "count": np.int32(7)})
+        files.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= (1 << 16) + 3 * 256   # (+ the .npy headers)
+    a, b = files
+    assert sorted(a) == ["actions_grad", "actions_grad_index", "count", "loss"]
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert a["loss"] == np.float32(-2.5) and a["count"] == 7.0
+    idx = a["actions_grad_index"].astype(np.int64)
+    assert np.array_equal(a["actions_grad_index"], idx) and np.all(np.diff(idx) > 0) and 0 < idx.size < big.size
+    assert np.array_equal(a["actions_grad"], big.reshape(-1)[idx])
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    # several ranks: one file per rank, the cap shared between them
+    bench.dump_outputs(str(tmp_path / "r"), {"loss": np.float64(1.0)}, rank=1, world=2)
+    assert os.listdir(tmp_path / "r") == ["loss_rank1.npy"] and np.load(tmp_path / "r" / "loss_rank1.npy").dtype == np.float64
+
+
 def test_dry_run_launches_two_ranks_on_cpu():
     out = _run(["--gpus", "2", "--dry-run", "--envs-per-gpu", "1024"], env={"CUDA_VISIBLE_DEVICES": "", "HIP_VISIBLE_DEVICES": ""})
     assert out.returncode == 0, out.stderr[-800:]
@@ -141,11 +177,11 @@ def test_world_size_must_match_label():
 
 @pytest.mark.gpu
 def test_bench_through_the_launcher_rccl_group_of_one():
-    out = _run(["--gpus", "1", "--launcher", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--strict"], timeout=900)
+    out = _run(["--gpus", "1", "--launcher", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--strict"], timeout=900)
     assert out.returncode == 0, out.stderr[-1500:]
     j = _json_line(out)
     assert j["n_gpus"] == 1 and j["rccl_ranks"] == 1 and j["steps"] == 2
-    # the other BASELINE.json configurations ride along in the default single-GPU line
+    # the other BASELINE.json configurations ride along in the --full single-GPU line
     def key(o):
         k = o["workload"].split()[0]
         return (k + ("_mm1" if o["workload"].endswith("frequency 1") else "") + ("_generic" if o["kernels"].startswith("generic") else "") +
@@ -177,6 +213,29 @@ def test_bench_through_the_launcher_rccl_group_of_one():
     assert abs(rf["alg_frac_step"] - 748 * full["value"] / 8e12) < 1e-9 and 0 < rf["alg_frac_step"] < 0.01
     if rf.get("counters"):   # counter file at these kernel sources: the flop view comes from the opcode census, not "every VALU op is an FMA"
         assert rf["fp32_valu_frac_est"] is None or rf["fp32_valu_frac_est"] < rf["fp32_valu_frac_upper_bound"]
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_and_dumps_the_same_outputs(tmp_path):
+    """a plain run (no --full): the headline figures only, and --dump-outputs writes what the last timed step returned -- the
+    same arrays, bit for bit, from two runs with the same arguments"""
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)], timeout=600)
+        assert out.returncode == 0, out.stderr[-1500:]
+        j = _json_line(out)
+        assert j["metric"] == "fwd+adjoint env-steps/sec" and j["unit"] == "env-steps/s" and j["higher_is_better"] is True
+        assert j["dtype"] == "f32" and j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 1e5
+        assert abs(j["value"] - 3 * 1024 * 32 / (3 * j["ms_per_step"] * 1e-3)) < 1e-3 * j["value"]
+        assert j["config"]["submission"] == "hip-graph" and j["config"]["submission_fallback"] is False
+        for k in ("roofline", "cpu_baseline", "other_configs", "eager_env_steps_per_s", "no_grad_forward_env_steps_per_s"):
+            assert k not in j, k
+        g, loss = np.load(d / "actions_grad.npy"), np.load(d / "loss.npy")
+        assert g.dtype == np.float32 and g.shape == (32, 1024, 8) and np.isfinite(g).all() and np.abs(g).sum() > 0
+        assert loss.dtype == np.float32 and loss.shape == () and np.isfinite(loss)
+        dumps.append((g, loss))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
 
 
 @pytest.mark.gpu

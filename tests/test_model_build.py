@@ -1,6 +1,6 @@
 """CPU-only: diffrl_amd's own asset loaders + ModelBuilder reproduce the reference's model constants
 (tests/golden/<env>_model.npz, dumped from the reference's builder) -- from the original asset files
-when they are available and from the compiled assets (.npz builder snapshots) always."""
+(stored copies under tests/golden/assets) and from the compiled assets (.npz builder snapshots)."""
 
 import os
 
@@ -17,6 +17,7 @@ FIELDS = ["joint_type", "joint_parent", "joint_q_start", "joint_qd_start", "join
           "body_I_m", "joint_armature", "joint_target", "joint_target_ke", "joint_target_kd", "joint_limit_lower",
           "joint_limit_upper", "joint_limit_ke", "joint_limit_kd", "contact_body", "contact_point", "contact_dist",
           "muscle_start", "muscle_links", "muscle_points", "gravity", "joint_q0"]
+ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "assets")
 
 
 def _check(env, t, exact):
@@ -46,14 +47,13 @@ def test_compiled_asset_matches_reference_model(env, cls, monkeypatch):
 
 @pytest.mark.parametrize("env,cls", CASES)
 def test_loader_matches_reference_model(env, cls, monkeypatch):
-    # the library only looks in $DIFFRL_ASSETS / its own assets dir: the test names the reference's asset dir explicitly
-    ref_assets = os.path.join(os.environ.get("DIFFRL_REFERENCE", "/root/reference"), "envs", "assets")
-    if os.path.isdir(ref_assets) and not os.environ.get("DIFFRL_ASSETS"):
-        monkeypatch.setenv("DIFFRL_ASSETS", ref_assets)
+    # the library only looks in $DIFFRL_ASSETS / its own assets dir: the test names its stored copies of the original asset
+    # files explicitly (tests/golden/assets, with their licences)
+    if not os.environ.get("DIFFRL_ASSETS"):
+        monkeypatch.setenv("DIFFRL_ASSETS", ASSETS)
     probe = {"ant": "ant.xml", "humanoid": "humanoid.xml", "snu": "snu/human.xml", "cartpole": "cartpole.urdf",
              "hopper": "hopper.xml", "cheetah": "half_cheetah.xml"}[env]
-    if de.find_asset(probe) is None:
-        pytest.skip("original asset files not available here")
+    assert de.find_asset(probe) is not None, probe
     e = cls(num_envs=2, device="cpu", no_grad=True)
     _check(env, e.model.template(), exact=True)
 

@@ -4,7 +4,7 @@ ENVN=$1; N=$2; shift 2
 for lib in "$@"; do
   echo "== $lib"
   DSIM_LIB=$PWD/$lib python tools/gpu_quick.py $ENVN $N 2>&1 | grep -v amdgpu.ids | grep -v "^AMD"
-  DSIM_LIB=$PWD/$lib python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs --env $ENVN --envs-per-gpu ${N%%,*} 2>/dev/null | python -c "
+  DSIM_LIB=$PWD/$lib python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-other-configs --env $ENVN --envs-per-gpu ${N%%,*} 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
