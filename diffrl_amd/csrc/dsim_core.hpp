@@ -154,9 +154,7 @@ DSIM_FN float dsim_range_sum_m(const float* data, int stride, int comp, int firs
 }
 // Bounds: whole lists for small trees (each lane makes one pass over its items); 8 for larger models, where the lanes
 // loop over several items and loading a long mostly-unused tail per item costs more issue slots than it saves latency.
-#ifndef DSIM_GENERIC_BATCH
 #define DSIM_GENERIC_BATCH 8   // entries the generic kernels' range sums request per round trip (the LDS image's spare tail covers the overrun)
-#endif
 template <class D> constexpr int dsim_cap_links() { return D::L <= 10 ? D::L : 8; }
 template <class D> constexpr int dsim_cap_subtree_contacts() { return D::C > 32 ? 8 : (D::C > 0 ? D::C : 1); }
 template <class D> constexpr int dsim_cap_body_contacts() { return D::C >= 8 ? 8 : (D::C > 0 ? D::C : 1); }
@@ -234,9 +232,7 @@ template <class Ctx, class Exec> DSIM_FN void dsim_init_static(const Ctx& c, Exe
 // trips per position in every substep.
 #define DSIM_CHAIN_MAX 10
 #define DSIM_SCAN_ROUNDS_MAX 4   // log-depth kinematics: trees of up to 16 levels
-#ifndef DSIM_SCAN_MIN_DEPTH
-#define DSIM_SCAN_MIN_DEPTH 5    // ... used from this many levels on (-DDSIM_SCAN_MIN_DEPTH=99 builds the A/B variant without it)
-#endif
+#define DSIM_SCAN_MIN_DEPTH 5    // ... used from this many levels on
 #define DSIM_TR_PASSES 2   // passes of the light items of a trunk-decomposed model over one wavefront
 // Per-lane topology records kept in REGISTERS by the specialised kernels (the executor owns one per lane).  A lane plays
 // the same roles in every substep -- link `lane`, dof `lane`, contact `lane` (forward) or `63 - lane` (adjoint) -- and the
@@ -276,9 +272,6 @@ struct DsimTopoRegs {
 // shifts.  DsimRowTreeFwd: the forward-pass counterparts (f_tot on registers, link <-> dof lane shifts), one-wave models only.
 template <class Ctx, class Exec> struct DsimRowTree {
     static constexpr bool value = []() {
-#ifdef DSIM_NO_ROWTREE   // (A/B builds)
-        return false;
-#else
         if constexpr (std::is_empty<decltype(Ctx::d)>::value) {
             using D = decltype(Ctx::d);
             const bool tree = D::RT_N > 0 && (D::flags & DSIM_F_RANGES) != 0;
@@ -286,7 +279,6 @@ template <class Ctx, class Exec> struct DsimRowTree {
         } else {
             return false;
         }
-#endif
     }();
 };
 // The HELPER wavefront brings the next checkpoint row into LDS (row-tree models with a helper wave, full checkpoint mode): it
@@ -296,12 +288,8 @@ template <class Ctx, class Exec> struct DsimRowTree {
 // barrier instead of the copy (register -> LDS stores + the store -> load turnaround in front of integrate^T).
 template <class Ctx, class Exec> struct DsimHelperCommit {
     static constexpr bool value = []() {
-#ifdef DSIM_NO_HELPER_COMMIT   // (A/B builds)
-        return false;
-#else
         if constexpr (DsimRowTree<Ctx, Exec>::value) return Exec::HAS_HELPER && !Ctx::LEAN && decltype(Ctx::d)::NS == 0;
         else return false;
-#endif
     }();
 };
 template <class Ctx, class Exec> struct DsimRowTreeFwd {
@@ -381,9 +369,6 @@ template <class Ctx, int NL> struct DsimContactRegs {  // contact `lane` / `63 -
 // (dsim_scan_fk_lane): the contact lanes no longer walk chains, they read published poses on the other wavefronts.
 template <class Ctx, class Exec> struct DsimWideOverlap {
     static constexpr bool value = []() {
-#ifdef DSIM_NO_WIDE_OVERLAP   // (A/B builds)
-        return false;
-#else
         if constexpr (std::is_empty<decltype(Ctx::d)>::value) {
             using D = decltype(Ctx::d);
             return Exec::NL >= 2 * DSIM_NL && D::NS > 0 && D::L < DSIM_NL && D::nd <= DSIM_NL && D::D <= (1 << DSIM_SCAN_ROUNDS_MAX) &&
@@ -391,7 +376,6 @@ template <class Ctx, class Exec> struct DsimWideOverlap {
         } else {
             return false;
         }
-#endif
     }();
 };
 // Log-depth forward kinematics (dsim_fwd_kinematics_scan) instead of the per-lane chain walk: specialised kernels with one
@@ -1801,17 +1785,13 @@ template <class Ctx, class Exec> struct DsimWaveGj {
         else return false;
     }();
 };
-// the mass matrix filled from its upper triangle (specialised kernels; -DDSIM_NO_SYM_FILL builds round 5's full fill for A/B runs)
+// the mass matrix filled from its upper triangle (specialised kernels; round 5 filled all of it)
 // One-wave mappings only: measured (tools/ab_min.py, profiles/r06_experiments.txt item 7) Ant forward -1.5 %, Humanoid -1.6 %; the
 // four-wave SNUHumanoid kernel +5 % (576 entries are 3 passes of its 256 lanes already; the folded index arithmetic and the
 // second store cost it more than the third pass did).
 template <class Ctx, class Exec> struct DsimSymFill {
     static constexpr bool value = []() {
-#ifdef DSIM_NO_SYM_FILL
-        return false;
-#else
         return DsimIsStatic<Ctx>::value && Exec::NL <= DSIM_NL;
-#endif
     }();
 };
 // H = J^T M J in composite-rigid-body form + armature, inverted in place (Gauss-Jordan, SPD, no pivoting)
@@ -2024,7 +2004,7 @@ DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float*
     static_assert(!Exec::HAS_HELPER || DsimScanFk<Ctx, Exec::NL>::value || DsimContactsAfterWalk<Ctx, Exec::NL>::value ||
                       DsimContactsInKin<Ctx, Exec::NL>::value,
                   "helper-wave kernels need a kinematics phase that starts with a workgroup barrier (tree too deep for the chain "
-                  "registers and the scan): build this model without a helper wavefront (dsim_has_helper)");
+                  "registers and the scan): build this model without a helper wavefront (dsim_hip.hip: dsim_has_mode)");
     ex.fork_mid_detached([&](int lane) {
         constexpr int MASK = dsim_tmask_static<Ctx>();
         constexpr int NQ = dsim_mask_nq(MASK), NDF = dsim_mask_nd(MASK);
@@ -2200,15 +2180,11 @@ DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float*
 // FIRST wavefront, the values changing lanes in registers (tau_j by v_readlane, qdd of a link's dofs by ds_bpermute), while the
 // others wait at ONE hand-over (mid: f_tot, tau and qdd are in LDS) and then copy the rest of the checkpoint row -- X_sc .. qdd,
 // which the integrator's stores do not touch -- beside the integrator.  Same arithmetic in the same order as dsim_tau_lane /
-// dsim_fwd_solve / dsim_integrate_lane.  (-DDSIM_NO_WIDE_DYN builds the three-phase form for A/B runs.)
+// dsim_fwd_solve / dsim_integrate_lane.
 template <class Ctx, class Exec> struct DsimWideDyn {
     static constexpr bool value = []() {
-#ifdef DSIM_NO_WIDE_DYN
-        return false;
-#else
         if constexpr (DsimWideOverlap<Ctx, Exec>::value) return decltype(Ctx::d)::nd <= 32 && decltype(Ctx::d)::L <= DSIM_NL;
         else return false;
-#endif
     }();
 };
 template <class Ctx, class Exec>
@@ -2510,14 +2486,9 @@ template <class Ctx, class Exec> DSIM_FN void dsim_hacc_zero(const Ctx& c, Exec&
 // v_readlane; adj qdd then travels by v_readlane into the rows of H^-1 each dof lane holds in registers (the mirror of the
 // forward's qdd = H^-1 tau), and adj tau stays in the register the per-dof block needs it in.  Two phase boundaries and the LDS
 // round trips of adj qdd and adj tau leave the critical path; same operations in the same order as the three phases.
-#ifndef DSIM_JW_ND_MAX
 #define DSIM_JW_ND_MAX 16
-#endif
 template <class Ctx, class Exec> struct DsimJointWave {
     static constexpr bool value = []() {
-#ifdef DSIM_NO_JOINT_WAVE   // (A/B builds)
-        return false;
-#else
         if constexpr (std::is_empty<decltype(Ctx::d)>::value && Exec::WAVE_OPS) {
             using D = decltype(Ctx::d);
             // measured (tools/ab_min.py, adjoint launch at 1024 environments): Ant -3.9 %; Humanoid (27 dofs: 27 rows of registers and
@@ -2527,7 +2498,6 @@ template <class Ctx, class Exec> struct DsimJointWave {
         } else {
             return false;
         }
-#endif
     }();
 };
 template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_wave(const Ctx& c, Exec& ex) {
@@ -3073,12 +3043,10 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_mass_bounded(const Ctx& c
 template <class Ctx, class Exec> DSIM_FN void dsim_bwd_mass(const Ctx& c, Exec& ex) {
     ex.mark(9);
     if constexpr (DsimIsStatic<Ctx>::value) {
-#ifndef DSIM_NO_BOUNDED_MASS   // (A/B builds)
         if constexpr ((decltype(c.d)::flags & DSIM_F_RANGES) != 0) {
             dsim_bwd_mass_bounded(c, ex);
             return;
         }
-#endif
     }
     const int nd = c.d.nd;
     ex.run([&](int lane) {

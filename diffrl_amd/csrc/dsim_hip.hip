@@ -23,7 +23,7 @@
 #include <string>
 
 #define DSIM_FN __device__ __forceinline__
-#ifndef DSIM_OPAQUE   // (-DDSIM_OPAQUE\(x\)= builds the A/B variant without it)
+#ifndef DSIM_OPAQUE
 #define DSIM_OPAQUE(x) asm volatile("" : "+v"(x))
 #endif
 #include "dsim_core.hpp"
@@ -51,19 +51,15 @@ namespace {
 __device__ __forceinline__ void dsim_wave_sync() { asm volatile(DSIM_WAVE_SYNC_ASM ::: "memory"); }
 
 // reciprocal of a pivot: v_rcp_f32 + one Newton step (< 1 ulp on the pivots of an SPD matrix; ~3 instead of the ~11 instructions
-// of the correctly rounded division on the pivot's dependent chain; -DDSIM_EXACT_DIV_SQRT builds the A/B variant with 1.0f / x)
+// of the correctly rounded division on the pivot's dependent chain)
 __device__ __forceinline__ float dsim_pivot_rcp(float x) {
-#if !defined(DSIM_EXACT_DIV_SQRT) && !defined(DSIM_EXACT_RCP)
     const float r = __builtin_amdgcn_rcpf(x);
     return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
-#else
-    return 1.0f / x;
-#endif
 }
 // Gauss-Jordan inverse with lane i holding row i in registers.  Per pivot k the classical in-place update is
 //   row k <- p = (row k with column k := 1) / h_kk;  row i <- (row i with column k := 0) - h_ik p        (dsim_core.hpp: dsim_fwd_mass)
-// i.e. per column: broadcast h_kj, scale it, multiply-add, select the pivot row: four instructions (-DDSIM_CLASSIC_GJ builds that
-// form for A/B runs; round 5 measured the deferred form below at -1 % .. -7 % of the forward launch, Ant .. SNUHumanoid).  The pivot
+// i.e. per column: broadcast h_kj, scale it, multiply-add, select the pivot row: four instructions (round 5 measured the
+// deferred form below at -1 % .. -7 % of the forward launch against it, Ant .. SNUHumanoid).  The pivot
 // row's scaling commutes with every LATER row operation (they are linear in the row), so lane k keeps its row UNSCALED -- column k
 // set to 1 -- remembers 1 / h_kk and scales once at the end; every other row takes f h_kj with f = h_ik / h_kk, lane k with f = 0:
 // per column one v_readlane and one multiply-add, no select.  Same elimination, different rounding (f h_kj instead of
@@ -75,7 +71,6 @@ template <int N, int NW> __device__ __forceinline__ void dsim_wave_gj(float* H) 
     float row[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) row[j] = H[r * N + j];
-#ifndef DSIM_CLASSIC_GJ
     float scale = 1.0f;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -93,20 +88,6 @@ template <int N, int NW> __device__ __forceinline__ void dsim_wave_gj(float* H) 
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) row[j] *= scale;
-#else
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const float piv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(row[k]), k));
-        const float rp = dsim_pivot_rcp(piv);
-        const float cik = row[k];
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const float hkj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(row[j]), k));
-            const float pj = (j == k ? 1.0f : hkj) * rp;
-            row[j] = (lane == k) ? pj : ((j == k ? 0.0f : row[j]) - cik * pj);
-        }
-    }
-#endif
     if (lane < N) {
 #pragma unroll
         for (int j = 0; j < N; ++j) H[lane * N + j] = row[j];
@@ -152,7 +133,6 @@ template <int N> __device__ __forceinline__ void dsim_half_gj(float* H, int lane
     float row[N];
 #pragma unroll
     for (int j = 0; j < N; ++j) row[j] = H[r * N + j];
-#ifndef DSIM_CLASSIC_GJ
     float scale = 1.0f;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -171,21 +151,6 @@ template <int N> __device__ __forceinline__ void dsim_half_gj(float* H, int lane
     }
 #pragma unroll
     for (int j = 0; j < N; ++j) row[j] *= scale;
-#else
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const int src = (k << 2) + half_addr;
-        const float piv = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(row[k])));
-        const float rp = dsim_pivot_rcp(piv);
-        const float cik = row[k];
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const float hkj = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(row[j])));
-            const float pj = (j == k ? 1.0f : hkj) * rp;
-            row[j] = (lane == k) ? pj : ((j == k ? 0.0f : row[j]) - cik * pj);
-        }
-    }
-#endif
     if (lane < N) {
 #pragma unroll
         for (int j = 0; j < N; ++j) H[lane * N + j] = row[j];
@@ -329,11 +294,6 @@ template <int NW, int PF = 6, int CW = 0, bool HELPER = false, int EPW = 1> stru
     __device__ __forceinline__ void add_from_above(float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float w) {
         static_assert(D >= 1 && D <= 15, "row shifts reach 1 .. 15 lanes");
         if constexpr (FIRST) asm volatile("s_nop 1" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5));
-#ifdef DSIM_NO_DPP_ASM   // (A/B builds: the builtin form)
-        a0 = __builtin_fmaf(from_above<D>(a0), w, a0); a1 = __builtin_fmaf(from_above<D>(a1), w, a1);
-        a2 = __builtin_fmaf(from_above<D>(a2), w, a2); a3 = __builtin_fmaf(from_above<D>(a3), w, a3);
-        a4 = __builtin_fmaf(from_above<D>(a4), w, a4); a5 = __builtin_fmaf(from_above<D>(a5), w, a5);
-#else
         asm volatile("v_fmac_f32_dpp %0, %0, %6 row_shl:%7 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
                      "v_fmac_f32_dpp %1, %1, %6 row_shl:%7 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
                      "v_fmac_f32_dpp %2, %2, %6 row_shl:%7 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
@@ -342,16 +302,13 @@ template <int NW, int PF = 6, int CW = 0, bool HELPER = false, int EPW = 1> stru
                      "v_fmac_f32_dpp %5, %5, %6 row_shl:%7 row_mask:0xf bank_mask:0xf bound_ctrl:1"
                      : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5)
                      : "v"(w), "n"(D));
-#endif
     }
     // every LDS load issued so far has landed: ONE s_waitcnt lgkmcnt(0) behind a batch of loads instead of the partial waits
     // (lgkmcnt(n), n counting down) the compiler otherwise puts in front of each first use.  A lone wave pays a full issue slot
     // (~4.6 cycles, tools/micro/issue_mix.hip) for every s_waitcnt, satisfied or not, while the loads of a batch return a few
     // cycles apart: after the phase's load batch the one full wait is cheaper than a dozen partial ones.
     __device__ __forceinline__ void loads_landed() {
-#ifndef DSIM_NO_FULL_WAIT   // (A/B builds)
         __builtin_amdgcn_s_waitcnt(0xC07F);   // vmcnt 63, expcnt 7, lgkmcnt 0
-#endif
     }
     // the same from the NEXT lane of the wave (wave_shl:1: crosses the 16-lane row boundaries; 0 into lane 63)
     template <bool FIRST = true>
@@ -684,14 +641,13 @@ template <int NW, int PF = 6, int CW = 0, bool HELPER = false, int EPW = 1> stru
 // needs 173 VGPRs, five over the 168 of three waves per SIMD: compiled for three it spills those to scratch and the Ant 8192
 // rollout drops from 18.4 M to 17.4 M env-steps/s (profiles/r04_pair_ab.txt), so two waves per SIMD (16 environments per CU,
 // plain mapping: 12) it is.
-#ifndef DSIM_PAIR_WAVES
 #define DSIM_PAIR_WAVES 0
-#endif
 // Kernels with several wavefronts per environment (SNUHumanoid: 4 waves, LDS for two environments per CU) need two resident waves
 // per SIMD -- 256 registers per lane, accumulation registers included: one more halves the environments in flight and doubles the
 // launch time (measured in round 5: the operator-level adjoint at 257: 0.29 -> 0.53 ms).  The bound makes the compiler keep to it.
 // (Not the lean-checkpoint kernels: their adjoint carries the forward phases too and would spill to scratch memory under it.)
 #define DSIM_WIDE_WAVES(NW) (((NW) > 1 && !LEAN) ? 2 : 0)
+#define DSIM_WAVES_WIDE 4   // wavefronts per environment of those kernels (pick_waves)
 #define DSIM_MODE_PLAIN 0
 #define DSIM_MODE_HELPER 1
 #define DSIM_MODE_PAIR 2
@@ -705,58 +661,46 @@ template <class O, class D> struct KCommonT {
     int* status;            // the model's two status words (host memory mapped into the device): dsim_check_unit_quats
 };
 
-// prefetch registers a model's checkpoint row needs (compile-time layouts), or the generic default of 6 (rows up to 1536 floats
-// at one wavefront per environment; longer rows are read at commit time)
-// models that get a helper wavefront: specialised one-wave kernels of models with ground contacts and without muscles
-// FWD: a forward kernel.  The GENERIC one-wave kernels (run-time layout) get a helper wavefront for their ADJOINT only (round 5):
-// its fork_join phases -- the af block beside the accumulators of adj H and the per-dof cotangents, contacts^T beside the per-link
-// block of the body level -- are the same phase code; the generic forward has no split phase, a helper would only idle there.
-template <class D, int NW, bool FWD = false> constexpr bool dsim_has_helper() {
-#ifdef DSIM_NO_HELPER
-    return false;
-#else
-    if constexpr (std::is_empty<D>::value) return NW == 1 && D::C > 0 && D::NS == 0 && D::L + D::C <= DSIM_NL;
-#ifdef DSIM_NO_GENERIC_HELPER   // (A/B builds)
-    else return false;
-#else
-    else return NW == 1 && !FWD;
-#endif
-#endif
+// Which step kernels exist: the kernel of direction FWD (a forward kernel) in launch mode MODE, for a model with layout types D
+// at NW wavefronts per environment.  Everything that names step kernels -- the launches (dsim_with_flags) and the table of a
+// model's kernels (for_each_step_kernel) -- asks here, so the code object holds exactly these.
+// HELPER: specialised one-wave kernels of models with ground contacts and without muscles, both directions.  The GENERIC
+// one-wave kernels (run-time layout) get a helper wavefront for their ADJOINT only (round 5): its fork_join phases -- the af
+// block beside the accumulators of adj H and the per-dof cotangents, contacts^T beside the per-link block of the body level --
+// are the same phase code; the generic forward has no split phase, a helper would only idle there.
+// PAIR: specialised one-wave models whose phases fit 32 lanes, forward direction only: the adjoint's LDS image (Ant 17 KB) caps
+// the environments per CU at the same 8 with either mapping, and a pair wave is 1.26 x as long as a plain one (measured,
+// profiles/r04_pair_ab.txt: Ant 8192 adjoint 0.287 ms plain, 0.349 ms pair).
+template <class D, int NW, bool FWD, int MODE> constexpr bool dsim_has_mode() {
+    if constexpr (MODE == DSIM_MODE_HELPER) {
+        if constexpr (std::is_empty<D>::value) return NW == 1 && D::C > 0 && D::NS == 0 && D::L + D::C <= DSIM_NL;
+        else return NW == 1 && !FWD;
+    } else if constexpr (MODE == DSIM_MODE_PAIR) {
+        return FWD && NW == 1 && dsim_pair_ok<D>();
+    } else {
+        return true;
+    }
 }
-// models that get two-environments-per-wave kernels: specialised one-wave models whose phases fit 32 lanes
-template <class D, int NW> constexpr bool dsim_has_pair() {
-#ifdef DSIM_NO_PAIR
-    return false;
-#else
-    return NW == 1 && dsim_pair_ok<D>();
-#endif
-}
-// f(lean, mode) with the two launch-time choices as compile-time constants.  `help` is false for models without helper
-// kernels, so they instantiate nothing extra.
-// FWD: a forward kernel.  Pair kernels exist for the forward direction only: the adjoint's LDS image (Ant 17 KB) caps the
-// environments per CU at the same 8 with either mapping, and a pair wave is 1.26 x as long as a plain one (measured,
-// profiles/r04_pair_ab.txt: Ant 8192 adjoint 0.287 ms plain, 0.349 ms pair; -DDSIM_PAIR_BWD builds them for A/B runs).
+using DsimPlainC = std::integral_constant<int, DSIM_MODE_PLAIN>;
+using DsimHelperC = std::integral_constant<int, DSIM_MODE_HELPER>;
+using DsimPairC = std::integral_constant<int, DSIM_MODE_PAIR>;
+// f(lean, mode) with the two launch-time choices as compile-time constants; a mode whose kernel does not exist for this model
+// and direction falls back to the plain kernel (and instantiates nothing).
 template <class D, int NW, bool FWD, class F> int dsim_with_flags(bool lean, int mode, F&& f) {
-    using M0 = std::integral_constant<int, DSIM_MODE_PLAIN>;
-    using M1 = std::integral_constant<int, DSIM_MODE_HELPER>;
-    using M2 = std::integral_constant<int, DSIM_MODE_PAIR>;
-    if constexpr (dsim_has_helper<D, NW, FWD>()) {
-        if (mode == DSIM_MODE_HELPER) return lean ? f(std::true_type{}, M1{}) : f(std::false_type{}, M1{});
+    if constexpr (dsim_has_mode<D, NW, FWD, DSIM_MODE_HELPER>()) {
+        if (mode == DSIM_MODE_HELPER) return lean ? f(std::true_type{}, DsimHelperC{}) : f(std::false_type{}, DsimHelperC{});
     }
-#ifdef DSIM_PAIR_BWD
-    constexpr bool pair_dir = true;
-#else
-    constexpr bool pair_dir = FWD;
-#endif
-    if constexpr (dsim_has_pair<D, NW>() && pair_dir) {
-        if (mode == DSIM_MODE_PAIR) return lean ? f(std::true_type{}, M2{}) : f(std::false_type{}, M2{});
+    if constexpr (dsim_has_mode<D, NW, FWD, DSIM_MODE_PAIR>()) {
+        if (mode == DSIM_MODE_PAIR) return lean ? f(std::true_type{}, DsimPairC{}) : f(std::false_type{}, DsimPairC{});
     }
-    return lean ? f(std::true_type{}, M0{}) : f(std::false_type{}, M0{});
+    return lean ? f(std::true_type{}, DsimPlainC{}) : f(std::false_type{}, DsimPlainC{});
 }
 template <class O> constexpr int dsim_const_words() {
     if constexpr (std::is_empty<O>::value) return O::const_words;
     else return 0;
 }
+// prefetch registers a model's checkpoint row needs (compile-time layouts), or the generic default of 6 (rows up to 1536 floats
+// at one wavefront per environment; longer rows are read at commit time)
 template <class O, int NW, bool LEAN, int MODE = 0> constexpr int dsim_pf_regs() {
     if constexpr (std::is_empty<O>::value) {
         // (several wavefronts: rows may be brought in by the wavefronts behind the first one alone, DevExec::prefetch_rest)
@@ -923,154 +867,6 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_body_xf_kernel(KCommonT<O, 
     dsim_body_transforms_only(c, ex, q + (size_t)e * k.d.nq, xsc + (size_t)e * 7 * k.d.L, xsm ? xsm + (size_t)e * 7 * k.d.L : nullptr);
 }
 
-#ifdef DSIM_ENABLE_PHASE_TIMER
-// developer tool (tools/phase_timer.py): per-phase cycle stamps of workgroup 0; NOT compiled into the product library
-template <int NW> struct TimingExec {
-    static constexpr int NL = DSIM_NL * NW;
-    static constexpr bool WAVE_OPS = NW == 1;
-    static constexpr bool WAVE0_OPS = true;
-    template <class F> __device__ __forceinline__ void run_wave0(F&& f) {
-        run([&](int lane) {
-            if (lane < DSIM_NL) f(lane);
-        });
-    }
-    __device__ __forceinline__ float shfl(float v, int src) {
-        return __int_as_float(__builtin_amdgcn_ds_bpermute(src << 2, __float_as_int(v)));
-    }
-    __device__ __forceinline__ float bcast(float v, int src) {
-        return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
-    }
-    __device__ __forceinline__ void lds_fence() { __syncthreads(); }
-    __device__ __forceinline__ void system_fence() { __threadfence_system(); }
-    long long* buf;
-    int idx, cap;
-    int tag = 0;
-    static constexpr bool HAS_HELPER = false;
-    template <class F> __device__ __forceinline__ void run_both(F&& f) { run(f); }
-    template <class FM, class FH> __device__ __forceinline__ void fork_join(FM&& fm, FH&& fh) {
-        run([&](int lane) {
-            fm(lane);
-            fh(lane);
-        });
-    }
-    template <class FM, class FH> __device__ __forceinline__ void fork_join_mid(FM&& fm, FH&& fh) { fork_join(fm, fh); }
-    template <class FM, class FH> __device__ __forceinline__ void fork_mid_detached(FM&& fm, FH&& fh) { fork_join(fm, fh); }
-    template <class FM, class FH> __device__ __forceinline__ void fork_side(FM&& fm, FH&& fh) {
-        run([&](int lane) {
-            fh(lane);
-            __syncthreads();
-            fm(lane);
-        });
-    }
-    __device__ __forceinline__ void side_done() { __syncthreads(); }
-    template <int D> __device__ __forceinline__ float from_above(float v) {
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + D, 0xf, 0xf, true));
-    }
-    template <int D> __device__ __forceinline__ float from_below(float v) {
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x110 + D, 0xf, 0xf, true));
-    }
-    template <int D, bool FIRST = true>
-    __device__ __forceinline__ void add_from_above(float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float w) {
-        a0 = __builtin_fmaf(from_above<D>(a0), w, a0); a1 = __builtin_fmaf(from_above<D>(a1), w, a1);
-        a2 = __builtin_fmaf(from_above<D>(a2), w, a2); a3 = __builtin_fmaf(from_above<D>(a3), w, a3);
-        a4 = __builtin_fmaf(from_above<D>(a4), w, a4); a5 = __builtin_fmaf(from_above<D>(a5), w, a5);
-    }
-    template <bool FIRST = true>
-    __device__ __forceinline__ void add_from_next(float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float w) {
-        auto nx = [](float v) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true)); };
-        a0 = __builtin_fmaf(nx(a0), w, a0); a1 = __builtin_fmaf(nx(a1), w, a1); a2 = __builtin_fmaf(nx(a2), w, a2);
-        a3 = __builtin_fmaf(nx(a3), w, a3); a4 = __builtin_fmaf(nx(a4), w, a4); a5 = __builtin_fmaf(nx(a5), w, a5);
-    }
-    template <int SRC>
-    __device__ __forceinline__ void add_from_lane(float& a0, float& a1, float& a2, float& a3, float& a4, float& a5, float w) {
-        const float s0 = bcast(a0, SRC), s1 = bcast(a1, SRC), s2 = bcast(a2, SRC), s3 = bcast(a3, SRC), s4 = bcast(a4, SRC), s5 = bcast(a5, SRC);
-        a0 = __builtin_fmaf(s0, w, a0); a1 = __builtin_fmaf(s1, w, a1); a2 = __builtin_fmaf(s2, w, a2);
-        a3 = __builtin_fmaf(s3, w, a3); a4 = __builtin_fmaf(s4, w, a4); a5 = __builtin_fmaf(s5, w, a5);
-    }
-    __device__ __forceinline__ void loads_landed() {}
-    __device__ __forceinline__ void group_sync() {}
-    __device__ __forceinline__ void helper_prefetch(const float*, int) {}
-    __device__ __forceinline__ void helper_commit(float*, int, const float*) {}
-    __device__ __forceinline__ void helper_prefetch_aux(const float*, int) {}
-    __device__ __forceinline__ void helper_commit_aux(float*, float*, int) {}
-    __device__ __forceinline__ void mid() { __syncthreads(); }
-    __device__ __forceinline__ void mid2() { if constexpr (NW > 1) __syncthreads(); }
-    __device__ __forceinline__ void side_done_w() { __syncthreads(); }
-    template <class F0, class FR> __device__ __forceinline__ void fork_wave0(F0&& f0, FR&& fr) {
-        run([&](int lane) {
-            if (lane < DSIM_NL) f0(lane);
-            else fr(lane - DSIM_NL);
-        });
-    }
-    __device__ __forceinline__ void stamp() {}
-    DsimImage<NW, 0> img_;
-    __device__ __forceinline__ void begin_request() {}
-    __device__ __forceinline__ void begin() { img_.land(); __syncthreads(); }
-    float io_[DSIM_IO_MAX];
-    __device__ __forceinline__ float* io(int) { return io_; }
-    __device__ __forceinline__ void mark(int t) { tag = t * 100; }
-    template <class F> __device__ __forceinline__ void run(F&& f) {
-        f((int)threadIdx.x);
-        __syncthreads();
-        if (blockIdx.x == 0 && threadIdx.x == 0 && idx < cap) {
-            buf[idx] = clock64();
-            buf[cap + idx] = tag;
-        }
-        ++tag;
-        ++idx;
-    }
-    template <class F> __device__ __forceinline__ void fire(F&& f) {
-        f((int)threadIdx.x);
-        if constexpr (NW > 1) __syncthreads();
-    }
-    template <int N> __device__ __forceinline__ void wave_gj(float* H) {
-        run([&](int) { dsim_wave_gj<N, NW>(H); });
-    }
-    static constexpr bool WAVE_GJ_PAD = true;
-    template <int NB> __device__ __forceinline__ void wave_gj_pad(float* H, int n) {
-        run([&](int) { dsim_wave_gj_pad<NB, NW>(H, n); });
-    }
-    float hacc_[DSIM_HACC_MAX];
-    __device__ __forceinline__ float* hacc(int) { return hacc_; }
-    float hpf_[DSIM_HPF_MAX];
-    __device__ __forceinline__ float* hpf(int) { return hpf_; }
-    DsimTopoRegs topo_;
-    __device__ __forceinline__ DsimTopoRegs& topo(int) { return topo_; }
-    const float* pf_src;
-    __device__ __forceinline__ void prefetch(const float* row, int) { pf_src = row; }
-    __device__ __forceinline__ void commit(float* dst, int words, int lane) {
-        for (int k = lane; k < words; k += NL) dst[k] = pf_src[k];
-    }
-    __device__ __forceinline__ void prefetch_rest(const float* row, int) { pf_src = row; }
-    __device__ __forceinline__ void commit_rest(float* dst, int words, int lane) {
-        for (int k = lane; k < words; k += NL - DSIM_NL) dst[k] = pf_src[k];
-    }
-};
-template <class O, class D, int NW>
-__global__ __launch_bounds__(DSIM_NL * NW) void dsim_timer_kernel(KCommonT<O, D> k, DsimEnvSpec sp, int backward,
-                                                             const float* q_in, const float* qd_in, const float* actions,
-                                                             float* q_out, float* qd_out, float* obs, float* rew,
-                                                             float* ckpt, const float* gq_out, const float* gqd_out,
-                                                             const float* gobs, const float* grew, float* gq_in,
-                                                             float* gqd_in, float* gactions, long long* stamps, int cap) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int e = blockIdx.x;
-    if (e >= k.n_envs) return;
-    TimingExec<NW> ex{stamps, 1, cap};
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
-    if (blockIdx.x == 0 && threadIdx.x == 0) stamps[0] = clock64();
-    const size_t nq = k.d.nq, nd = k.d.nd;
-    float* ck = ckpt + (size_t)e * k.ckpt_stride;
-    if (!backward)
-        dsim_env_fused_forward(c, ex, sp, k.substeps, k.mm_freq, q_in + e * nq, qd_in + e * nd,
-                               actions + (size_t)e * sp.n_act, q_out + e * nq, qd_out + e * nd,
-                               obs + (size_t)e * sp.n_obs, rew + e, ck, DsimEpisode{}, e, k.n_envs);
-    else
-        dsim_env_fused_backward(c, ex, sp, k.substeps, k.mm_freq, ck, actions + (size_t)e * sp.n_act, gq_out + e * nq,
-                                gqd_out + e * nd, gobs + (size_t)e * sp.n_obs, grew + e, nullptr, gq_in + e * nq,
-                                gqd_in + e * nd, gactions + (size_t)e * sp.n_act);
-}
-#endif
 
 thread_local std::string g_err;
 
@@ -1130,16 +926,11 @@ struct dsim_model {
     int pair_min_envs = 1 << 30;
     int mode(int n_envs, bool fwd) const {
         if (helper_ok(n_envs)) return DSIM_MODE_HELPER;
-#ifndef DSIM_PAIR_BWD
         if (!fwd) return DSIM_MODE_PLAIN;
-#endif
         return n_envs >= pair_min_envs ? DSIM_MODE_PAIR : DSIM_MODE_PLAIN;
     }
 };
 void dsim_helper_capacity(dsim_model* m);
-#ifndef DSIM_WAVES_WIDE
-#define DSIM_WAVES_WIDE 4   // (-DDSIM_WAVES_WIDE=2 builds the A/B variant)
-#endif
 
 namespace {
 
@@ -1238,6 +1029,69 @@ int launched(const char* what) {
     return DSIM_OK;
 }
 
+// The four families of step kernels (a function template cannot be a template argument; a family names its kernels).
+#define DSIM_STEP_FAMILY(NAME, IS_FWD)                                                      \
+    struct NAME##_family {                                                                  \
+        static constexpr bool FWD = IS_FWD;                                                 \
+        static constexpr const char* what = "launch " #NAME;                                \
+        template <class O, class D, int NW, bool LEAN, int MODE> static constexpr auto kernel() { return &NAME<O, D, NW, LEAN, MODE>; } \
+    };
+DSIM_STEP_FAMILY(dsim_bwd_kernel, false)
+DSIM_STEP_FAMILY(dsim_env_bwd_kernel, false)
+DSIM_STEP_FAMILY(dsim_fwd_kernel, true)
+DSIM_STEP_FAMILY(dsim_env_fwd_kernel, true)
+#undef DSIM_STEP_FAMILY
+
+// f(kernel, is_forward, lean, mode) for every step kernel of a model: operator and env step, forward and adjoint, full and lean
+// checkpoints, every launch mode in which the kernel exists (dsim_has_mode).
+template <class O, class D, int NW, class F> void for_each_step_kernel(F&& f) {
+    auto one = [&](auto fam, auto lean_c, auto mode_c) {
+        using Fam = decltype(fam);
+        constexpr bool LEAN = decltype(lean_c)::value;
+        constexpr int MODE = decltype(mode_c)::value;
+        if constexpr (dsim_has_mode<D, NW, Fam::FWD, MODE>())
+            f(reinterpret_cast<const void*>(Fam::template kernel<O, D, NW, LEAN, MODE>()), Fam::FWD, LEAN, MODE);
+    };
+    auto mode = [&](auto mode_c) {
+        auto lean = [&](auto lean_c) {
+            one(dsim_bwd_kernel_family{}, lean_c, mode_c);
+            one(dsim_env_bwd_kernel_family{}, lean_c, mode_c);
+            one(dsim_fwd_kernel_family{}, lean_c, mode_c);
+            one(dsim_env_fwd_kernel_family{}, lean_c, mode_c);
+        };
+        lean(std::false_type{});
+        lean(std::true_type{});
+    };
+    mode(DsimPlainC{});
+    mode(DsimHelperC{});
+    mode(DsimPairC{});
+}
+
+// The one launch site of the step kernels: kernel variant, wave count, checkpoint mode and launch mode become compile-time
+// constants, and the geometry follows from them -- EPB environments per workgroup (2 in pair mode), one workgroup of NW waves
+// (+ the helper wave) each, and the LDS image(s) of the direction (a pair shares one copy of the model constants: start_env).
+// `args`: the kernel's arguments behind its KCommonT.
+template <class Fam, class... Args>
+int launch_step(const dsim_model* m, int n_envs, float dt, int substeps, int mm_freq, void* hip_stream, Args... args) {
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return dispatch(m, [&](auto o, auto d, auto nw) {
+        using O = decltype(o);
+        using D = decltype(d);
+        constexpr int NW = decltype(nw)::value;
+        auto k = make_k(m, o, d, n_envs, dt, substeps, mm_freq);
+        const size_t image_words = Fam::FWD ? m->lay.o.fwd_words : m->lay.o.total_words, const_words = m->lay.o.const_words;
+        dsim_with_flags<D, NW, Fam::FWD>(m->lean, m->mode(n_envs, Fam::FWD), [&](auto lean_c, auto mode_c) {
+            constexpr bool LEAN = decltype(lean_c)::value;
+            constexpr int MODE = decltype(mode_c)::value, EPB = MODE == DSIM_MODE_PAIR ? 2 : 1;
+            hipLaunchKernelGGL((Fam::template kernel<O, D, NW, LEAN, MODE>()), dim3((n_envs + EPB - 1) / EPB),
+                               dim3(DSIM_NL * NW * (MODE == DSIM_MODE_HELPER ? 2 : 1)),
+                               (image_words * EPB - const_words * (EPB - 1)) * 4, st, k, args...);
+            return 0;
+        });
+        return launched(Fam::what);
+    });
+}
+
 int make_spec(const dsim_model* m, const dsim_env_spec* e, DsimEnvSpec& sp) {
     if (!e) return fail(DSIM_ERR_INVALID, "null env spec");
     const DsimDims& d = m->lay.d;
@@ -1318,37 +1172,9 @@ int dsim_model_create(const dsim_model_desc* desc, dsim_model** out) {
             using O = decltype(o);
             using D = decltype(d);
             constexpr int NW = decltype(nw)::value;
-            auto raise = [&](auto mode_c) {
-                constexpr int HELP = decltype(mode_c)::value;
-                const void* fns[] = {reinterpret_cast<const void*>(dsim_bwd_kernel<O, D, NW, false, HELP>),
-                                     reinterpret_cast<const void*>(dsim_env_bwd_kernel<O, D, NW, false, HELP>),
-                                     reinterpret_cast<const void*>(dsim_fwd_kernel<O, D, NW, false, HELP>),
-                                     reinterpret_cast<const void*>(dsim_env_fwd_kernel<O, D, NW, false, HELP>),
-                                     reinterpret_cast<const void*>(dsim_bwd_kernel<O, D, NW, true, HELP>),
-                                     reinterpret_cast<const void*>(dsim_env_bwd_kernel<O, D, NW, true, HELP>),
-                                     reinterpret_cast<const void*>(dsim_fwd_kernel<O, D, NW, true, HELP>),
-                                     reinterpret_cast<const void*>(dsim_env_fwd_kernel<O, D, NW, true, HELP>)};
-                for (const void* fn : fns)
-                    if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            };
-            raise(std::integral_constant<int, DSIM_MODE_PLAIN>{});
-            if constexpr (dsim_has_helper<D, NW, true>()) raise(std::integral_constant<int, DSIM_MODE_HELPER>{});
-            else if constexpr (dsim_has_helper<D, NW, false>()) {   // (generic kernels: helper-wave ADJOINT kernels only)
-                const void* fns[] = {reinterpret_cast<const void*>(dsim_bwd_kernel<O, D, NW, false, DSIM_MODE_HELPER>),
-                                     reinterpret_cast<const void*>(dsim_env_bwd_kernel<O, D, NW, false, DSIM_MODE_HELPER>),
-                                     reinterpret_cast<const void*>(dsim_bwd_kernel<O, D, NW, true, DSIM_MODE_HELPER>),
-                                     reinterpret_cast<const void*>(dsim_env_bwd_kernel<O, D, NW, true, DSIM_MODE_HELPER>)};
-                for (const void* fn : fns)
-                    if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            }
-            if constexpr (dsim_has_pair<D, NW>()) {
-                const void* fns[] = {reinterpret_cast<const void*>(dsim_fwd_kernel<O, D, NW, false, DSIM_MODE_PAIR>),
-                                     reinterpret_cast<const void*>(dsim_env_fwd_kernel<O, D, NW, false, DSIM_MODE_PAIR>),
-                                     reinterpret_cast<const void*>(dsim_fwd_kernel<O, D, NW, true, DSIM_MODE_PAIR>),
-                                     reinterpret_cast<const void*>(dsim_env_fwd_kernel<O, D, NW, true, DSIM_MODE_PAIR>)};
-                for (const void* fn : fns)
-                    if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            }
+            for_each_step_kernel<O, D, NW>([&](const void* fn, bool, bool, int) {
+                if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            });
             if (e == hipSuccess)
                 e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_env_obs_kernel<O, D, NW>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1378,33 +1204,22 @@ void dsim_helper_capacity(dsim_model* m) {
         using O = decltype(o);
         using D = decltype(d);
         constexpr int NW = decltype(nw)::value;
-        if constexpr (dsim_has_helper<D, NW>()) {
+        if constexpr (dsim_has_mode<D, NW, false, DSIM_MODE_HELPER>()) {
             int cus = 0, per_cu = 1 << 20;   // (callers have the model's device current: dsim_model_create, check_device)
             bool ok = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device) == hipSuccess;
-            auto cap = [&](auto kernel, int words) {   // resident workgroups per CU of one helper kernel
+            // resident workgroups per CU of each helper kernel (the lean ones count once the model is in that mode: it is chosen
+            // right after creation, and dsim_model_set_ckpt_mode re-evaluates)
+            for_each_step_kernel<O, D, NW>([&](const void* fn, bool fwd, bool lean, int mode) {
+                if (mode != DSIM_MODE_HELPER || (lean && !m->lean)) return;
+                const size_t words = fwd ? m->lay.o.fwd_words : m->lay.o.total_words;
                 int n = 0;
-                ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 2 * DSIM_NL, (size_t)words * 4) == hipSuccess;
+                ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 2 * DSIM_NL, words * 4) == hipSuccess;
                 if (n < per_cu) per_cu = n;
-            };
-            constexpr bool FWD_TOO = dsim_has_helper<D, NW, true>();   // (generic kernels: the adjoint alone)
-            cap(dsim_env_bwd_kernel<O, D, NW, false, DSIM_MODE_HELPER>, m->lay.o.total_words);
-            cap(dsim_bwd_kernel<O, D, NW, false, DSIM_MODE_HELPER>, m->lay.o.total_words);
-            if constexpr (FWD_TOO) {
-                cap(dsim_env_fwd_kernel<O, D, NW, false, DSIM_MODE_HELPER>, m->lay.o.fwd_words);
-                cap(dsim_fwd_kernel<O, D, NW, false, DSIM_MODE_HELPER>, m->lay.o.fwd_words);
-            }
-            if (m->lean) {   // (the mode is chosen right after creation; dsim_model_set_ckpt_mode re-evaluates)
-                cap(dsim_env_bwd_kernel<O, D, NW, true, DSIM_MODE_HELPER>, m->lay.o.total_words);
-                cap(dsim_bwd_kernel<O, D, NW, true, DSIM_MODE_HELPER>, m->lay.o.total_words);
-                if constexpr (FWD_TOO) {
-                    cap(dsim_env_fwd_kernel<O, D, NW, true, DSIM_MODE_HELPER>, m->lay.o.fwd_words);
-                    cap(dsim_fwd_kernel<O, D, NW, true, DSIM_MODE_HELPER>, m->lay.o.fwd_words);
-                }
-            }
+            });
             m->helper_max_envs = ok ? cus * per_cu : 0;
             if (const char* f = getenv("DSIM_HELPER")) m->helper_max_envs = atoi(f) ? (1 << 30) : 0;
         }
-        if constexpr (dsim_has_pair<D, NW>()) {
+        if constexpr (dsim_has_mode<D, NW, true, DSIM_MODE_PAIR>()) {
             m->pair_min_envs = 0;
             if (const char* f = getenv("DSIM_PAIR")) m->pair_min_envs = atoi(f) ? 0 : (1 << 30);
         }
@@ -1455,19 +1270,8 @@ int dsim_step_forward(const dsim_model* m, int n_envs, const float* q_in, const 
     if (rc) return rc;
     if (!q_in || !qd_in || !act || !q_out || !qd_out) return fail(DSIM_ERR_INVALID, "null state pointer");
     if (m->lay.d.M > 0 && !muscle_act) return fail(DSIM_ERR_INVALID, "model has muscles but muscle_act is null");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, dt, substeps, mm_freq);
-        dsim_with_flags<decltype(d), NW, true>(m->lean, m->mode(n_envs, true), [&](auto lean_c, auto mode_c) {
-            constexpr bool LEAN = decltype(lean_c)::value;
-            constexpr int MODE = decltype(mode_c)::value, EPB = MODE == DSIM_MODE_PAIR ? 2 : 1;
-            hipLaunchKernelGGL((dsim_fwd_kernel<decltype(o), decltype(d), NW, LEAN, MODE>), dim3((n_envs + EPB - 1) / EPB),
-                           dim3(DSIM_NL * NW * (MODE == DSIM_MODE_HELPER ? 2 : 1)), ((size_t)m->lay.o.fwd_words * EPB - (size_t)m->lay.o.const_words * (EPB - 1)) * 4, st, k, q_in, qd_in, act, muscle_act, q_out, qd_out, ckpt);
-            return 0;
-        });
-        return launched("launch dsim_fwd_kernel");
-    });
+    return launch_step<dsim_fwd_kernel_family>(m, n_envs, dt, substeps, mm_freq, hip_stream, q_in, qd_in, act, muscle_act, q_out,
+                                               qd_out, ckpt);
 }
 
 static int step_backward(const dsim_model* m, int n_envs, const float* ckpt, const float* act, const float* muscle_act,
@@ -1478,20 +1282,8 @@ static int step_backward(const dsim_model* m, int n_envs, const float* ckpt, con
     if (!ckpt || !act || !gq_out || !gqd_out || !gq_in || !gqd_in)
         return fail(DSIM_ERR_INVALID, "null pointer (ckpt/act/grad)");
     if (m->lay.d.M > 0 && !muscle_act) return fail(DSIM_ERR_INVALID, "model has muscles but muscle_act is null");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, dt, substeps, mm_freq);
-        dsim_with_flags<decltype(d), NW, false>(m->lean, m->mode(n_envs, false), [&](auto lean_c, auto mode_c) {
-            constexpr bool LEAN = decltype(lean_c)::value;
-            constexpr int MODE = decltype(mode_c)::value, EPB = MODE == DSIM_MODE_PAIR ? 2 : 1;
-            hipLaunchKernelGGL((dsim_bwd_kernel<decltype(o), decltype(d), NW, LEAN, MODE>), dim3((n_envs + EPB - 1) / EPB),
-                           dim3(DSIM_NL * NW * (MODE == DSIM_MODE_HELPER ? 2 : 1)), ((size_t)m->lay.o.total_words * EPB - (size_t)m->lay.o.const_words * (EPB - 1)) * 4, st, k, ckpt, act, muscle_act, gq_out, gqd_out, gq_in, gqd_in,
-                           gact, gmuscle_act, lit);
-            return 0;
-        });
-        return launched("launch dsim_bwd_kernel");
-    });
+    return launch_step<dsim_bwd_kernel_family>(m, n_envs, dt, substeps, mm_freq, hip_stream, ckpt, act, muscle_act, gq_out, gqd_out,
+                                               gq_in, gqd_in, gact, gmuscle_act, lit);
 }
 
 int dsim_step_backward(const dsim_model* m, int n_envs, const float* ckpt, const float* act, const float* muscle_act,
@@ -1557,20 +1349,8 @@ int dsim_env_step_forward(const dsim_model* m, const dsim_env_spec* env, int n_e
         ep.noise_angle = episode->noise_angle;
         ep.seed = episode->seed;
     }
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, dt, substeps, mm_freq);
-        dsim_with_flags<decltype(d), NW, true>(m->lean, m->mode(n_envs, true), [&](auto lean_c, auto mode_c) {
-            constexpr bool LEAN = decltype(lean_c)::value;
-            constexpr int MODE = decltype(mode_c)::value, EPB = MODE == DSIM_MODE_PAIR ? 2 : 1;
-            hipLaunchKernelGGL((dsim_env_fwd_kernel<decltype(o), decltype(d), NW, LEAN, MODE>), dim3((n_envs + EPB - 1) / EPB),
-                           dim3(DSIM_NL * NW * (MODE == DSIM_MODE_HELPER ? 2 : 1)), ((size_t)m->lay.o.fwd_words * EPB - (size_t)m->lay.o.const_words * (EPB - 1)) * 4, st, k, sp, ep, q_in, qd_in, actions, q_out, qd_out, obs, rew,
-                           ckpt);
-            return 0;
-        });
-        return launched("launch dsim_env_fwd_kernel");
-    });
+    return launch_step<dsim_env_fwd_kernel_family>(m, n_envs, dt, substeps, mm_freq, hip_stream, sp, ep, q_in, qd_in, actions, q_out,
+                                                   qd_out, obs, rew, ckpt);
 }
 
 int dsim_env_step_backward(const dsim_model* m, const dsim_env_spec* env, int n_envs, const float* ckpt,
@@ -1583,20 +1363,8 @@ int dsim_env_step_backward(const dsim_model* m, const dsim_env_spec* env, int n_
     rc = make_spec(m, env, sp);
     if (rc) return rc;
     if (!ckpt || !actions || !gq_in || !gqd_in || !gactions) return fail(DSIM_ERR_INVALID, "null pointer");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, dt, substeps, mm_freq);
-        dsim_with_flags<decltype(d), NW, false>(m->lean, m->mode(n_envs, false), [&](auto lean_c, auto mode_c) {
-            constexpr bool LEAN = decltype(lean_c)::value;
-            constexpr int MODE = decltype(mode_c)::value, EPB = MODE == DSIM_MODE_PAIR ? 2 : 1;
-            hipLaunchKernelGGL((dsim_env_bwd_kernel<decltype(o), decltype(d), NW, LEAN, MODE>), dim3((n_envs + EPB - 1) / EPB),
-                           dim3(DSIM_NL * NW * (MODE == DSIM_MODE_HELPER ? 2 : 1)), ((size_t)m->lay.o.total_words * EPB - (size_t)m->lay.o.const_words * (EPB - 1)) * 4, st, k, sp, ckpt, actions, gq_out, gqd_out, gobs, grew,
-                           gobs_before_reset, gq_in, gqd_in, gactions);
-            return 0;
-        });
-        return launched("launch dsim_env_bwd_kernel");
-    });
+    return launch_step<dsim_env_bwd_kernel_family>(m, n_envs, dt, substeps, mm_freq, hip_stream, sp, ckpt, actions, gq_out, gqd_out,
+                                                   gobs, grew, gobs_before_reset, gq_in, gqd_in, gactions);
 }
 
 int dsim_env_observe(const dsim_model* m, const dsim_env_spec* env, int n_envs, const float* q, const float* qd,
@@ -1645,28 +1413,6 @@ int dsim_debug_stamps(long long* out, int n) {
         if (e == hipSuccess) e = hipMemset(sym, 0, sizeof(long long) * 2 * 16384);
     }
     return e == hipSuccess ? DSIM_OK : hip_fail(e, "dsim_debug_stamps");
-}
-#endif
-#ifdef DSIM_ENABLE_PHASE_TIMER
-int dsim_debug_phase_timer(const dsim_model* m, const dsim_env_spec* env, int n_envs, int backward, const float* q_in,
-                           const float* qd_in, const float* actions, float dt, int substeps, int mm_freq, float* q_out,
-                           float* qd_out, float* obs, float* rew, float* ckpt, const float* gq_out, const float* gqd_out,
-                           const float* gobs, const float* grew, float* gq_in, float* gqd_in, float* gactions,
-                           long long* stamps, int cap, void* hip_stream) {
-    int rc = check_common(m, n_envs, dt, substeps, mm_freq);
-    if (rc) return rc;
-    DsimEnvSpec sp;
-    rc = make_spec(m, env, sp);
-    if (rc) return rc;
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, dt, substeps, mm_freq);
-        hipLaunchKernelGGL((dsim_timer_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
-                           (size_t)m->lay.o.total_words * 4, static_cast<hipStream_t>(hip_stream), k, sp, backward, q_in,
-                           qd_in, actions, q_out, qd_out, obs, rew, ckpt, gq_out, gqd_out, gobs, grew, gq_in, gqd_in, gactions,
-                           stamps, cap);
-        return launched("launch dsim_timer_kernel");
-    });
 }
 #endif
 

@@ -94,7 +94,7 @@ DSIM_FN q4 rotate_adj_q(q4 q, v3 x, v3 r) {
 // 1 / sqrt(n2) for the normalisation of a quaternion (0 for n2 == 0: the reference's normalize() leaves a zero quaternion alone,
 // quat.h:70-83).  Device code: v_rsq_f32 + one Newton step -- as accurate as the reference's two correctly rounded operations
 // (square root, division) together (< 1 ulp), ~6 instead of ~30 dependent instructions on the one lane that integrates the free
-// root; not the same bits (-DDSIM_EXACT_DIV_SQRT builds the A/B variant; the host harness of tests/emu always takes that path).
+// root; not the same bits (the host harness of tests/emu always takes the correctly rounded path).
 // v_rsq_f32 flushes a denormal input to zero: rsq = +inf, and the correction steps then make inf - inf = NaN.  A squared length
 // below the smallest normal (a tangential contact velocity of ~1e-19, a quaternion of that norm) is treated as zero length,
 // like the exactly-zero case: the force / rotation it would scale is below 1e-15 of anything else in the step.
@@ -134,24 +134,10 @@ DSIM_FN float dsim_inv_len_two_step(float n2) {
 // sampled Humanoid environments (tools/ant_grad_probe.py; the pivots' v_rcp_f32 + Newton and the muscle segments' one-step
 // form changed nothing) -- these are the values friction regimes and contact thresholds hang on, and the quantity the integrator
 // renormalises 512 times per rollout.  They keep the reference's two roundings (dsim_inv_len_two_step: same counts as the
-// correctly rounded operations; -DDSIM_INTEG_RSQ builds the one-step form).
-DSIM_FN float dsim_inv_len(float n2) {
-#if defined(DSIM_EXACT_DIV_SQRT) || defined(DSIM_EXACT_RSQ_INTEG)
-    return dsim_inv_len_exact(n2);
-#elif defined(DSIM_INTEG_RSQ)
-    return dsim_inv_len_fast(n2);
-#else
-    return dsim_inv_len_two_step(n2);
-#endif
-}
+// correctly rounded operations).
+DSIM_FN float dsim_inv_len(float n2) { return dsim_inv_len_two_step(n2); }
 // ... of a muscle segment (per-item lanes; a smooth function of the poses, no thresholds)
-DSIM_FN float dsim_inv_len_item(float n2) {
-#if defined(DSIM_EXACT_DIV_SQRT) || defined(DSIM_EXACT_RSQ_ITEM)
-    return dsim_inv_len_exact(n2);
-#else
-    return dsim_inv_len_fast(n2);
-#endif
-}
+DSIM_FN float dsim_inv_len_item(float n2) { return dsim_inv_len_fast(n2); }
 // sin/cos of a joint half-angle.  Joint angles live inside their limits (|q| <= ~pi), so |x| <= pi/2 is the
 // hot case: odd/even Taylor polynomials to x^11 / x^12 (truncation error < 6e-8 at pi/2, i.e. below fp32
 // resolution) -- ~14 FMAs instead of two library calls with full range reduction; anything larger falls

@@ -1,5 +1,6 @@
 #!/bin/bash
 # Developer tool (runs on the GPU box): tools/ab.sh <env> <N> lib1.so lib2.so ... -> kernel timings + output hashes per library
+# (libraries from tools/dev_build.sh; a variant is built from a second worktree or a local edit, not with a committed switch)
 ENVN=$1; N=$2; shift 2
 for lib in "$@"; do
   echo "== $lib"

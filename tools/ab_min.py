@@ -1,5 +1,7 @@
 """Developer tool (GPU box): A/B kernel timings that survive box-to-box and run-to-run noise -- the libraries are measured in
 alternation (several rounds, each library in its own process), the MINIMUM per library and kernel is reported.
+The libraries come from tools/dev_build.sh; a variant is built from a second worktree or a local edit of the kernel sources,
+not with a committed build switch.
 usage: python tools/ab_min.py <env> <N> <rounds> lib1.so lib2.so ..."""
 import os
 import re
