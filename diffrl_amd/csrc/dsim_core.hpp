@@ -2449,6 +2449,144 @@ DSIM_FN void dsim_body_transforms_only(const Ctx& c, Exec& ex, const float* g_q,
     });
 }
 
+// Differentiable kinematic read-out of a given (q, qd) (dsim_body_kinematics / dsim_body_kinematics_backward, include/dsim.h):
+// X_sc, X_sm as above and the world-frame spatial twists v_s [L][6] = (w, v) of every link about the WORLD ORIGIN (the
+// reference's body_v_s, sim.py:1716-1789: the velocity of a point p of the link is v + w x p) -- the kinematics phase of the
+// step kernels on the caller's q AND qd -- and the reverse pass from cotangents on the three tensors to cotangents on (q, qd).
+// Plain code on the general helpers (dsim_subtree_sum is valid for every kernel variant): one kinematics pass, not a substep loop.
+template <class Ctx, class Exec> DSIM_FN void dsim_body_kin_load(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd) {
+    ex.begin_request();
+    ex.begin();
+    dsim_init_static(c, ex);
+    ex.run_both([&](int lane) { dsim_topo_init<false>(c, ex, lane); });
+    ex.run([&](int lane) {
+        for (int k = lane; k < c.d.nq; k += Exec::NL) WF(q)[k] = g_q[k];
+        for (int k = lane; k < c.d.nd; k += Exec::NL) WF(qd)[k] = g_qd ? g_qd[k] : 0.f;   // no qd: poses only
+    });
+}
+template <class Ctx, class Exec>
+DSIM_FN void dsim_body_kin_forward(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, float* g_xsc, float* g_xsm,
+                                   float* g_vs, int* g_status = nullptr, int env = 0) {
+    dsim_body_kin_load(c, ex, g_q, g_qd);
+    dsim_check_unit_quats(c, ex, g_status, env);
+    dsim_fwd_kinematics(c, ex);
+    ex.run([&](int lane) {
+        for (int it = lane; it < 7 * c.d.L; it += Exec::NL) g_xsc[it] = WF(xsc)[it];
+        if (g_vs)
+            for (int it = lane; it < 6 * c.d.L; it += Exec::NL) g_vs[it] = WF(v)[it];
+        if (g_xsm) {
+            for (int i = lane; i < c.d.L; i += Exec::NL) {
+                const v3 p = ld3(WF(xsc) + 7 * i);
+                const q4 r = ldq(WF(xsc) + 7 * i + 3);
+                const v3 pm = rotate(r, ld3(CF(com) + 3 * i)) + p;
+                float* o = g_xsm + 7 * i;
+                o[0] = pm.x; o[1] = pm.y; o[2] = pm.z; o[3] = r.x; o[4] = r.y; o[5] = r.z; o[6] = r.w;
+            }
+        }
+    });
+}
+// The reverse pass, in the wrench form of dsim_bwd_bodies (the cotangent arrays of the adjoint image are re-used):
+//   1. a pose cotangent (gp, gr) of a frame at p with rotation r is the world-frame wrench (p x gp + 1/2 vec(gr (x) conj(r)), gp)
+//      on its link -- the component of gr along r drops out (it has no meaning on the unit sphere); X_sm rides on the link with
+//      r_sm = r_sc (joint_X_cm has an identity rotation);
+//   2. v_i = sum over the ancestors-or-self j of vj_j, vj = S qd: with A_i the subtree sum of the twist cotangents,
+//      adj qd_d = S_d . A_link(d);
+//   3. the motion subspace of a non-free joint is attached to the joint frame X_sj, i.e. to the PARENT link (the free joint's is
+//      the constant identity): the parent receives the wrench Wp_i = (vj.w x A.w + vj.v x A.v, vj.w x A.v);
+//   4. a joint coordinate moves the subtree of its link rigidly: with Wt_i the subtree sum of the wrenches (Wp_i is added to
+//      link i's own row so that every proper ancestor's sum has it, and taken off Wt_i again), hinge / prismatic
+//      adj q = S . Wt; ball 2 (t, 0) (x) q with t_k = S_k . Wt; free R_j^T f and 2 (R_j^T (tau - p_c x f), 0) (x) q_r.
+// Cotangent pointers may be null (= zeros).  Every word of g_gq (and g_gqd) is WRITTEN by the lane of the link that owns it:
+// no atomics, the result does not depend on the launch.  The quaternion blocks of g_gq have no component along the quaternion.
+template <class Ctx, class Exec>
+DSIM_FN void dsim_body_kin_backward(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, const float* g_gxsc,
+                                    const float* g_gxsm, const float* g_gvs, float* g_gq, float* g_gqd) {
+    dsim_body_kin_load(c, ex, g_q, g_qd);
+    dsim_fwd_kinematics(c, ex);
+    ex.run([&](int lane) {
+        for (int i = lane; i < c.d.L; i += Exec::NL) {
+            const v3 p = ld3(WF(xsc) + 7 * i);
+            const q4 r = ldq(WF(xsc) + 7 * i + 3);
+            v3 f = zero3(), tau = zero3();
+            q4 gr = mkq(0.f, 0.f, 0.f, 0.f);
+            if (g_gxsc) {
+                const v3 gp = ld3(g_gxsc + 7 * i);
+                f += gp;
+                tau += cross(p, gp);
+                gr += ldq(g_gxsc + 7 * i + 3);
+            }
+            if (g_gxsm) {
+                const v3 pm = rotate(r, ld3(CF(com) + 3 * i)) + p;
+                const v3 gp = ld3(g_gxsm + 7 * i);
+                f += gp;
+                tau += cross(pm, gp);
+                gr += ldq(g_gxsm + 7 * i + 3);
+            }
+            tau += qvec(qmul(gr, qconj(r))) * 0.5f;
+            stsv(WF(aw) + 6 * i, mksv(tau, f));
+            stsv(WF(av) + 6 * i, g_gvs ? ldsv(g_gvs + 6 * i) : zerosv());
+        }
+    });
+    ex.run([&](int lane) {
+        for (int it = lane; it < 6 * c.d.L; it += Exec::NL) {
+            const int i = it / 6, k = it - 6 * i;
+            WF(aatot)[it] = dsim_subtree_sum(c, WF(av), 6, k, i);
+        }
+    });
+    ex.run([&](int lane) {
+        for (int i = lane; i < c.d.L; i += Exec::NL) {
+            const int type = CI(jtype)[i], ds = CI(qdstart)[i];
+            const int ndj = CI(qdstart)[i + 1] - ds;
+            const sv6 A = ldsv(WF(aatot) + 6 * i);
+            sv6 vj = zerosv();
+            for (int k = 0; k < ndj; ++k) {
+                const sv6 S = ldsv(WF(S) + 6 * (ds + k));
+                vj += S * WF(qd)[ds + k];
+                if (g_gqd) g_gqd[ds + k] = sdot(S, A);
+            }
+            sv6 Wp = zerosv();
+            if (type != DSIM_JOINT_FREE) {
+                Wp.w = cross(vj.w, A.w) + cross(vj.v, A.v);
+                Wp.v = cross(vj.w, A.v);
+            }
+            stsv(WF(aw) + 6 * i, ldsv(WF(aw) + 6 * i) + Wp);
+            stsv(WF(awp) + 6 * i, Wp);
+        }
+    });
+    ex.run([&](int lane) {
+        for (int it = lane; it < 6 * c.d.L; it += Exec::NL) {
+            const int i = it / 6, k = it - 6 * i;
+            WF(azs)[it] = dsim_subtree_sum(c, WF(aw), 6, k, i);
+        }
+    });
+    ex.run([&](int lane) {
+        constexpr int MASK = dsim_tmask_static<Ctx>();
+        for (int i = lane; i < c.d.L; i += Exec::NL) {
+            const int type = CI(jtype)[i], cs = CI(qstart)[i], ds = CI(qdstart)[i], par = CI(parent)[i];
+            const sv6 Wt = ldsv(WF(azs) + 6 * i) - ldsv(WF(awp) + 6 * i);
+            if (type == DSIM_JOINT_PRISMATIC || type == DSIM_JOINT_REVOLUTE) g_gq[cs] = sdot(ldsv(WF(S) + 6 * ds), Wt);
+            if constexpr ((MASK & DSIM_TM(DSIM_JOINT_BALL)) != 0) {
+                if (type == DSIM_JOINT_BALL) {
+                    const v3 t = mk3(sdot(ldsv(WF(S) + 6 * ds), Wt), sdot(ldsv(WF(S) + 6 * ds + 6), Wt),
+                                     sdot(ldsv(WF(S) + 6 * ds + 12), Wt));
+                    stq(g_gq + cs, qmul_v(t, ldq(WF(q) + cs)) * 2.0f);
+                }
+            }
+            if constexpr ((MASK & DSIM_TM(DSIM_JOINT_FREE)) != 0) {
+                if (type == DSIM_JOINT_FREE) {
+                    // X_sc = X_sj o (q_p, q_r): translation by R_j dq_p, rotation about p_c
+                    const v3 pc = ld3(WF(xsc) + 7 * i);
+                    q4 rj = ldq(CF(xpj) + 7 * i + 3);
+                    if (par >= 0) rj = qmul(ldq(WF(xsc) + 7 * par + 3), rj);
+                    const v3 tc = Wt.w - cross(pc, Wt.v);
+                    st3(g_gq + cs, rotate_inv(rj, Wt.v));
+                    stq(g_gq + cs + 3, qmul_v(rotate_inv(rj, tc), ldq(WF(q) + cs + 3)) * 2.0f);
+                }
+            }
+        }
+    });
+}
+
 // ================================================================================================
 // adjoint (hand-derived reverse sweep of one substep)
 // ================================================================================================

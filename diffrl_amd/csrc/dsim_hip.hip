@@ -868,6 +868,39 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_body_xf_kernel(KCommonT<O, 
 }
 
 
+// Differentiable kinematic read-out (dsim_core.hpp: dsim_body_kin_forward / dsim_body_kin_backward): one environment per
+// workgroup, plain launch mode.  The forward kernel needs the forward image only; the adjoint re-runs the kinematics phase and
+// uses the cotangent arrays of the adjoint image.
+template <class O, class D, int NW>
+__global__ __launch_bounds__(DSIM_NL * NW) void dsim_body_kin_kernel(KCommonT<O, D> k, const float* __restrict__ q,
+                                                                   const float* __restrict__ qd, float* xsc, float* xsm, float* vs) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, 6, dsim_const_words<O>(), false> ex;
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex);
+    const size_t L = k.d.L;
+    dsim_body_kin_forward(c, ex, q + (size_t)e * k.d.nq, qd ? qd + (size_t)e * k.d.nd : nullptr, xsc + e * 7 * L,
+                          xsm ? xsm + e * 7 * L : nullptr, vs ? vs + e * 6 * L : nullptr, k.status, e);
+}
+
+template <class O, class D, int NW>
+__global__ __launch_bounds__(DSIM_NL * NW) void dsim_body_kin_bwd_kernel(KCommonT<O, D> k, const float* __restrict__ q,
+                                                                       const float* __restrict__ qd, const float* __restrict__ gxsc,
+                                                                       const float* __restrict__ gxsm, const float* __restrict__ gvs,
+                                                                       float* gq, float* gqd) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, 6, dsim_const_words<O>(), false> ex;
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    const size_t L = k.d.L;
+    dsim_body_kin_backward(c, ex, q + (size_t)e * k.d.nq, qd ? qd + (size_t)e * k.d.nd : nullptr, gxsc ? gxsc + e * 7 * L : nullptr,
+                           gxsm ? gxsm + e * 7 * L : nullptr, gvs ? gvs + e * 6 * L : nullptr, gq + (size_t)e * k.d.nq,
+                           gqd ? gqd + (size_t)e * k.d.nd : nullptr);
+}
+
+
 thread_local std::string g_err;
 
 int fail(int code, const std::string& msg) {
@@ -1131,7 +1164,7 @@ int make_spec(const dsim_model* m, const dsim_env_spec* e, DsimEnvSpec& sp) {
 extern "C" {
 
 const char* dsim_last_error(void) { return g_err.c_str(); }
-int dsim_version(void) { return 107; }
+int dsim_version(void) { return 108; }
 
 int dsim_model_create(const dsim_model_desc* desc, dsim_model** out) {
     if (!desc || !out) return fail(DSIM_ERR_INVALID, "null argument");
@@ -1180,6 +1213,12 @@ int dsim_model_create(const dsim_model_desc* desc, dsim_model** out) {
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e == hipSuccess)
                 e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_body_xf_kernel<O, D, NW>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_body_kin_kernel<O, D, NW>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_body_kin_bwd_kernel<O, D, NW>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             return 0;
         });
@@ -1397,6 +1436,40 @@ int dsim_body_transforms(const dsim_model* m, int n_envs, const float* q, float*
         hipLaunchKernelGGL((dsim_body_xf_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
                            (size_t)m->lay.o.fwd_words * 4, st, k, q, X_sc, X_sm);
         return launched("launch dsim_body_xf_kernel");
+    });
+}
+
+int dsim_body_kinematics(const dsim_model* m, int n_envs, const float* q, const float* qd, float* X_sc, float* X_sm, float* v_s,
+                         void* hip_stream) {
+    int rc = check_common(m, n_envs, 1.0f, 1, 1);
+    if (rc) return rc;
+    if (!q || !X_sc) return fail(DSIM_ERR_INVALID, "null pointer");
+    if ((qd == nullptr) != (v_s == nullptr)) return fail(DSIM_ERR_INVALID, "v_s is returned if and only if qd is given");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return dispatch(m, [&](auto o, auto d, auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
+        hipLaunchKernelGGL((dsim_body_kin_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
+                           (size_t)m->lay.o.fwd_words * 4, st, k, q, qd, X_sc, X_sm, v_s);
+        return launched("launch dsim_body_kin_kernel");
+    });
+}
+
+int dsim_body_kinematics_backward(const dsim_model* m, int n_envs, const float* q, const float* qd, const float* gX_sc,
+                                  const float* gX_sm, const float* gv_s, float* gq, float* gqd, void* hip_stream) {
+    int rc = check_common(m, n_envs, 1.0f, 1, 1);
+    if (rc) return rc;
+    if (!q || !gq) return fail(DSIM_ERR_INVALID, "null pointer");
+    if ((qd == nullptr) != (gqd == nullptr)) return fail(DSIM_ERR_INVALID, "gqd is returned if and only if qd is given");
+    if (!qd && gv_s) return fail(DSIM_ERR_INVALID, "gv_s without qd: there is no v_s output to have a cotangent");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return dispatch(m, [&](auto o, auto d, auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
+        k.status = nullptr;   // the forward launch checked the state
+        hipLaunchKernelGGL((dsim_body_kin_bwd_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
+                           (size_t)m->lay.o.total_words * 4, st, k, q, qd, gX_sc, gX_sm, gv_s, gq, gqd);
+        return launched("launch dsim_body_kin_bwd_kernel");
     });
 }
 

@@ -452,5 +452,12 @@ class Model:
             self._engine = Engine(self.template(), self.device)
         return self._engine
 
+    def body_kinematics(self, state):
+        """(body_X_sc, body_X_sm, body_v_s) of state.joint_q / joint_qd, shaped like the reference's State tensors
+        ([link_count, 7], [link_count, 7], [link_count, 6]) and DIFFERENTIABLE in both (Engine.body_kinematics): a loss written
+        on a link's pose or twist back-propagates into the joint state and, through the step that produced it, into the actions.
+        These are the frames of the state handed in; State.body_X_sc keeps the reference's one-substep lag and no grad_fn."""
+        return self.engine().body_kinematics(state.joint_q, state.joint_qd)
+
     def flatten(self):
         return [v for v in self.__dict__.values() if torch.is_tensor(v)]

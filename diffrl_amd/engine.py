@@ -125,6 +125,49 @@ class Engine:
             self._ck(self._lib.dsim_body_transforms(self._h, n, _ptr(q), _ptr(xsc), _ptr(xsm), st))
         return xsc, xsm
 
+    def body_kinematics(self, q, qd=None):
+        """(X_sc, X_sm, v_s | None): link frames, centre-of-mass frames ([n_envs * n_links, 7]) and -- if qd is given -- the
+        world-frame spatial twists (w, v) of the links about the world origin ([n_envs * n_links, 6], the reference's
+        State.body_v_s: the velocity of a point p of a link is v + w x p) of the joint state (q, qd) HANDED IN, differentiable in
+        q and qd (BodyKinematics below; one launch forward, one backward).  body_transforms is the detached read-back."""
+        if qd is None:
+            return BodyKinematics.apply(self, q, None) + (None,)
+        return BodyKinematics.apply(self, q, qd)
+
+    def body_kinematics_forward(self, q, qd=None):
+        """dsim_body_kinematics on detached contiguous tensors"""
+        self._check(q, self.n_q, "joint_q")
+        n = q.numel() // self.n_q
+        if qd is not None:
+            self._check(qd, self.n_qd, "joint_qd")
+            if qd.numel() != n * self.n_qd:
+                raise capi.DsimError("state tensors disagree on the number of environments")
+        L = self.template.n_links
+        xsc = torch.empty((n * L, 7), dtype=torch.float32, device=self.device)
+        xsm = torch.empty((n * L, 7), dtype=torch.float32, device=self.device)
+        vs = torch.empty((n * L, 6), dtype=torch.float32, device=self.device) if qd is not None else None
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self._ck(self._lib.dsim_body_kinematics(self._h, n, _ptr(q), _ptr(qd), _ptr(xsc), _ptr(xsm), _ptr(vs), st))
+        return xsc, xsm, vs
+
+    def body_kinematics_backward(self, q, qd, gxsc, gxsm, gvs):
+        """dsim_body_kinematics_backward: any cotangent may be None (= zeros, no buffer); -> (gq, gqd | None), flat"""
+        n = q.numel() // self.n_q
+        L = self.template.n_links
+        for g, cols, name in ((gxsc, 7, "gX_sc"), (gxsm, 7, "gX_sm"), (gvs, 6, "gv_s")):
+            if g is not None:
+                self._check(g, cols, name)
+                if g.numel() != n * L * cols:
+                    raise capi.DsimError("%s has the wrong size" % name)
+        gq = torch.empty(n * self.n_q, dtype=torch.float32, device=self.device)
+        gqd = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device) if qd is not None else None
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self._ck(self._lib.dsim_body_kinematics_backward(self._h, n, _ptr(q), _ptr(qd), _ptr(gxsc), _ptr(gxsm), _ptr(gvs),
+                                                               _ptr(gq), _ptr(gqd), st))
+        return gq, gqd
+
     def last_substep_q(self, ckpt, substeps):
         """joint_q ENTERING the last substep of the step that wrote `ckpt` (the head of that substep's checkpoint row): what the
         reference's eval_rigid_fk saw when it filled the returned State's body_X_sc (sim.py:2316-2601)."""
@@ -325,6 +368,33 @@ class EnvStep(torch.autograd.Function):
         gq, gqd, ga = ctx.engine.env_backward(ctx.spec, ckpt, actions, ctx.dt, ctx.substeps, ctx.mm_freq, c(gq_out),
                                               c(gqd_out), c(gobs), c(grew), c(gobs_before))
         return None, None, None, None, None, None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), ga.view(ctx.shapes[2])
+
+
+class BodyKinematics(torch.autograd.Function):
+    """(joint_q, joint_qd | None) -> (X_sc, X_sm[, v_s]): the kinematic read-out of a joint state with its adjoint
+    (dsim_body_kinematics / dsim_body_kinematics_backward); the backward launch re-runs the kinematics on the saved (q, qd).
+    The quaternion blocks of the returned joint_q gradient have no component along the quaternion, as SimStep's."""
+
+    @staticmethod
+    def forward(ctx, engine, q, qd):
+        qc = q.detach().contiguous()
+        qdc = qd.detach().contiguous() if qd is not None else None
+        xsc, xsm, vs = engine.body_kinematics_forward(qc, qdc)
+        ctx.engine = engine
+        ctx.has_qd = qd is not None
+        ctx.shapes = (q.shape, qd.shape if qd is not None else None)
+        ctx.set_materialize_grads(False)   # an output the loss does not read costs no cotangent buffer
+        ctx.save_for_backward(qc, qdc if qdc is not None else qc.new_empty(0))
+        return (xsc, xsm, vs) if qd is not None else (xsc, xsm)
+
+    @staticmethod
+    def backward(ctx, gxsc, gxsm, gvs=None):
+        if gxsc is None and gxsm is None and gvs is None:
+            return None, None, None
+        q, qd = ctx.saved_tensors
+        c = lambda g: g.contiguous() if g is not None else None  # noqa: E731
+        gq, gqd = ctx.engine.body_kinematics_backward(q, qd if ctx.has_qd else None, c(gxsc), c(gxsm), c(gvs))
+        return None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]) if ctx.has_qd else None
 
 
 class SimStep(torch.autograd.Function):

@@ -199,6 +199,26 @@ int dsim_step_backward_literal(const dsim_model* m, int n_envs,
  * reference's literal value: the head of the last substep's checkpoint row, which is that substep's input q). */
 int dsim_body_transforms(const dsim_model* m, int n_envs, const float* q, float* X_sc, float* X_sm, void* hip_stream);
 
+/* Differentiable body kinematics: link poses and twists of a given joint state, and the reverse pass.
+ *   X_sc [N][L][7], X_sm [N][L][7]   as above, OF THE q HANDED IN (not the reference's one-substep lag, which stays a property
+ *                                    of the State tensors the integrator returns);
+ *   v_s  [N][L][6]                   world-frame spatial twist (w, v) of every link about the WORLD ORIGIN -- the reference's
+ *                                    State.body_v_s (sim.py:1716-1789): the velocity of a point p of the link is v + w x p.
+ * qd may be NULL: poses only, and v_s must be NULL too (v_s is returned if and only if qd is given); X_sm may be NULL.
+ * The backward call maps cotangents on the three tensors (each may be NULL = zeros) to cotangents on q and qd, which are
+ * WRITTEN, not accumulated (gqd is returned if and only if qd is given; gv_s needs qd).  It re-runs the kinematics on (q, qd):
+ * nothing is kept between the two calls.  Pose cotangents are treated as world-frame wrenches, so, as
+ * for the step adjoint above, the quaternion blocks of gq have NO component along the quaternion -- project the reference's
+ * literal gradient onto the tangent space before comparing.
+ * Like every call here: device pointers borrowed for the call, launches on the caller's stream, no host synchronisation,
+ * deterministic (no atomics).  Precondition: unit quaternions in q; the forward call checks it like the step functions do (the
+ * NEXT call on the model returns DSIM_ERR_INVALID), the backward call does not check again. */
+int dsim_body_kinematics(const dsim_model* m, int n_envs, const float* q, const float* qd /* may be NULL */,
+                         float* X_sc, float* X_sm /* may be NULL */, float* v_s /* NULL iff qd is NULL */, void* hip_stream);
+int dsim_body_kinematics_backward(const dsim_model* m, int n_envs, const float* q, const float* qd /* may be NULL */,
+                                  const float* gX_sc, const float* gX_sm, const float* gv_s /* each may be NULL = zeros */,
+                                  float* gq, float* gqd /* NULL iff qd is NULL */, void* hip_stream);
+
 /* ---- fused environment surface -------------------------------------
  * The per-step torch glue of the reference environments -- action clip + scale into joint_act /
  * muscle activations (envs/ant.py:157-163, humanoid.py:188-211, snu_humanoid.py:245-271,
