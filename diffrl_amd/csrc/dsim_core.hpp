@@ -30,6 +30,7 @@
 
 #include "dsim_layout.hpp"
 #include "dsim_math.hpp"
+#include "dsim_math_quad.hpp"
 
 // DSIM_OPAQUE(x): the kernels define it as an empty asm that "modifies" x.  Used on the per-lane joint type / chain length
 // read from the register-resident topology records at the top of a phase: otherwise every lane predicate derived from
@@ -231,6 +232,7 @@ template <class Ctx, class Exec> DSIM_FN void dsim_init_static(const Ctx& c, Exe
 // LDS tables once per launch (dsim_topo_init) instead of as an index -> record -> data chain of three dependent LDS round
 // trips per position in every substep.
 #define DSIM_CHAIN_MAX 10
+#define DSIM_QUAD_DEPTH 4   // deepest tree the quad kinematics take (DsimQuadKin)
 #define DSIM_SCAN_ROUNDS_MAX 4   // log-depth kinematics: trees of up to 16 levels
 #define DSIM_SCAN_MIN_DEPTH 5    // ... used from this many levels on
 #define DSIM_TR_PASSES 2   // passes of the light items of a trunk-decomposed model over one wavefront
@@ -263,6 +265,13 @@ struct DsimTopoRegs {
     // (selects, not 1 / 0 weight registers: the records live in registers for the whole launch, of BOTH waves)
     int gx_row[DSIM_GX_PASSES], gx_n[DSIM_GX_PASSES];
     int gf_row[3], gf_n[3];                  // the same for the forward pass's contact wrench rows (6 components per item, 6 L <= 192 items)
+    // quad kinematics (DsimQuadKin): the walker's link (lane / 4 in the four-lanes-per-link layout, else lane; 0 and qk_on = 0
+    // past the last link), its joint type and first dof; per chain position (joint, q start, qd start) and a weight -- 1, or 0
+    // for the identity positions that pad a chain shorter than the tree is deep; the lane constants of dsim_math_quad.hpp
+    int qk_i, qk_on, qk_type, qk_ods;
+    int qk_link[DSIM_QUAD_DEPTH], qk_cs[DSIM_QUAD_DEPTH], qk_ds[DSIM_QUAD_DEPTH];
+    float qk_w[DSIM_QUAD_DEPTH];
+    DsimQuadConsts qc;
 };
 
 // Row-tree form of the body-level adjoint (dsim_bwd_bodies_rowtree): specialised kernels of pre-order trees of at most 32 links
@@ -423,6 +432,25 @@ template <class Ctx, int NL> struct DsimContactsInKin {
         else return false;
     }();
 };
+// Quad form of that phase (dsim_fwd_kinematics_walk_quad, dsim_math_quad.hpp): trees of at most DSIM_QUAD_DEPTH levels whose root
+// is the only free joint, with revolute joints below it and identity joint-frame rotations throughout (Ant).  QUAD: four lanes
+// per link, one vector component each, where 4 L lanes exist; otherwise (two environments per wavefront: 32 lanes) the same
+// source with one link per lane -- the same IEEE operations in the same order, bit-identical results.
+template <class Ctx, int NL> struct DsimQuadKin {
+    static constexpr bool value = []() {
+        if constexpr (DsimContactsAfterWalk<Ctx, NL>::value) {
+            using D = decltype(Ctx::d);
+            bool ok = D::D >= 1 && D::D <= DSIM_QUAD_DEPTH && D::pmask[0] == DSIM_TM(DSIM_JOINT_FREE) &&
+                      (D::pident & ((1 << D::D) - 1)) == ((1 << D::D) - 1);
+            for (int p = 1; p < D::D; ++p) ok = ok && D::pmask[p] == DSIM_TM(DSIM_JOINT_REVOLUTE);
+            return ok;
+        } else return false;
+    }();
+    static constexpr bool QUAD = []() {
+        if constexpr (value) return 4 * decltype(Ctx::d)::L <= NL;
+        else return false;
+    }();
+};
 // ADJ: the launch runs adjoint phases (the forward kernels skip the records only those use)
 template <bool ADJ = true, class Ctx, class Exec> DSIM_FN void dsim_topo_init(const Ctx& c, Exec& ex, int lane) {
     if constexpr (DsimTrunk<Ctx, Exec>::value) {
@@ -500,6 +528,35 @@ template <bool ADJ = true, class Ctx, class Exec> DSIM_FN void dsim_topo_init(co
             ch[4 * p + 3] = li.ds;
         }
         ch[4 * DSIM_CHAIN_MAX] = n;
+    }
+    if constexpr (DsimQuadKin<Ctx, Exec::NL>::value) {
+        using D = decltype(c.d);
+        DsimTopoRegs& tp = ex.topo(lane);
+        const int li = DsimQuadKin<Ctx, Exec::NL>::QUAD ? lane >> 2 : lane;
+        const int i = li < D::L ? li : 0;
+        const int e0 = CI(anc_start)[i], n = CI(anc_start)[i + 1] - e0;
+        tp.qk_i = i;
+        tp.qk_on = li < D::L ? 1 : 0;
+        tp.qk_type = CI(jtype)[i];
+        tp.qk_ods = CI(qdstart)[i];
+        // position 0 is the root; the link's other ancestors-or-self fill the LAST positions, so that the link's own joint is
+        // always the last one; the positions in between are identities (weight 0 on the root's record: finite values, all
+        // multiplied by 0)
+#pragma unroll
+        for (int p = 0; p < D::D; ++p) {
+            const int k = p - (D::D - n);
+            const bool real = p == 0 || k >= 1;
+            const int j = CI(anc_list)[e0 + ((p > 0 && real) ? k : 0)];
+            const DsimLinkInfo info = dsim_link_info(c, j);
+            tp.qk_link[p] = j;
+            tp.qk_cs[p] = info.cs;
+            tp.qk_ds[p] = info.ds;
+            tp.qk_w[p] = real ? 1.f : 0.f;
+            DSIM_OPAQUE(tp.qk_w[p]);
+        }
+        dsim_quad_consts_init(tp.qc, lane);
+        DSIM_OPAQUE(tp.qc.ex); DSIM_OPAQUE(tp.qc.ey); DSIM_OPAQUE(tp.qc.ez);
+        DSIM_OPAQUE(tp.qc.kx); DSIM_OPAQUE(tp.qc.ky); DSIM_OPAQUE(tp.qc.kz); DSIM_OPAQUE(tp.qc.qs);
     }
     if constexpr (DsimRoleRegs<Ctx, Exec::NL>::value) {
         DsimTopoRegs& tp = ex.topo(lane);
@@ -1325,6 +1382,146 @@ template <class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics_walk_mid(const
     });
 }
 
+// The same phase in the quad form (DsimQuadKin): B is the backend of dsim_math_quad.hpp -- four lanes per link with one vector
+// component each, or one link per lane.  All loads first, no store before the end of the walk; every lane runs the whole block
+// with the same sequence of cross-lane operations (positions a chain does not have are identities, not skipped), and the
+// phase's interface is the one-link-per-lane form's: same words of xsc, v, a, i10, f, S.
+template <class Ctx, class Exec, class B> DSIM_FN void dsim_fk_quad_block(const Ctx& c, Exec& ex, const B& b, const DsimTopoRegs& tp) {
+    using D = decltype(c.d);
+    typedef typename B::T T;
+    typedef DsimQuadSv<B> SV;
+    const int i = tp.qk_i;
+    int on = tp.qk_on, own_type = tp.qk_type;
+    DSIM_OPAQUE(on);
+    DSIM_OPAQUE(own_type);
+    const float *q = WF(q), *qd = WF(qd);
+    // ---- loads: the root's coordinates and velocity, (X_pj translation, axis, angle, rate) of the positions below it, body constants
+    const T qp = b.template ld<3>(q + tp.qk_cs[0]), qr = b.template ld<4>(q + tp.qk_cs[0] + 3);
+    SV v, a, s0;
+    v.w = b.template ld<3>(qd + tp.qk_ds[0]);
+    v.v = b.template ld<3>(qd + tp.qk_ds[0] + 3);
+    T ppj[D::D], ax[D::D];
+    float ang[D::D], rate[D::D];
+    ppj[0] = b.template ld<3>(CF(xpj) + 7 * tp.qk_link[0]);
+#pragma unroll
+    for (int p = 1; p < D::D; ++p) {
+        ppj[p] = b.template ld<3>(CF(xpj) + 7 * tp.qk_link[p]);
+        ax[p] = b.template ld<3>(CF(axis) + 3 * tp.qk_link[p]);
+        ang[p] = q[tp.qk_cs[p]];
+        rate[p] = qd[tp.qk_ds[p]];
+    }
+    const T com = b.template ld<3>(CF(com) + 3 * i), grav = b.template ld<3>(CF(grav));
+    const float* icp = CF(ic6) + 6 * i;
+    const float ic0 = icp[0], ic1 = icp[1], ic2 = icp[2], ic3 = icp[3], ic4 = icp[4], ic5 = icp[5];
+    const float m = CF(mass)[i];
+    // ---- root: free joint with an identity frame; v = v_j, a = 0
+    T psp = b.add(qp, ppj[0]), rsp = qr;
+    a.w = a.v = s0.w = s0.v = b.spl(0.f);
+    // ---- revolute positions
+#pragma unroll
+    for (int p = 1; p < D::D; ++p) {
+        float wgt = tp.qk_w[p];
+        DSIM_OPAQUE(wgt);
+        const DsimQuadRot<B> R = dq_rot_pre(b, rsp);
+        const T pj = b.add(dq_rotate(b, R, dq_scale(b, ppj[p], wgt)), psp);
+        float sn, cs;
+        half_angle_sincos(ang[p] * wgt * 0.5f, sn, cs);
+        const T qa = b.sel_w(dq_scale(b, ax[p], sn), b.spl(cs));
+        const T u = dq_rotate(b, R, ax[p]);
+        s0.w = u;
+        s0.v = dq_cross(b, pj, u);
+        const float r = rate[p] * wgt;
+        SV vj;
+        vj.w = dq_scale(b, s0.w, r);
+        vj.v = dq_scale(b, s0.v, r);
+        v.w = b.add(v.w, vj.w);
+        v.v = b.add(v.v, vj.v);
+        a = dq_scross_acc(b, a, v, vj);
+        psp = pj;
+        rsp = dq_qmul(b, rsp, qa);
+    }
+    if (on) {
+        b.template st<4>(WF(xsc) + 7 * i + 3, rsp);
+        if (b.xyz()) {
+            b.template st<3>(WF(xsc) + 7 * i, psp);
+            b.template st<3>(WF(v) + 6 * i, v.w);
+            b.template st<3>(WF(v) + 6 * i + 3, v.v);
+        }
+    }
+    ex.stamp();
+    ex.mid();   // poses and twists of every link are in LDS: the contacts may start
+    // ---- COM, world inertia about the origin and body force
+    const DsimQuadBody<B> body = dq_body_inertia_force(b, rsp, psp, com, grav, m, ic0, ic1, ic2, ic3, ic4, ic5, a, v);
+    const DsimQuadI<B>& I = body.I;
+    const SV& f = body.f;
+    if (on && b.xyz()) {
+        b.template st<3>(WF(a) + 6 * i, a.w);
+        b.template st<3>(WF(a) + 6 * i + 3, a.v);
+        // i10 = (m, h, axx, axy, axz, ayy, ayz, azz): row 0, then (y, z) of row 1 and z of row 2.  No two lanes write different
+        // values to a word (m goes to its word from all three lanes): the compiler is free to reorder or pair (ds_write2) the
+        // stores of one lane, so nothing may depend on their order.
+        float* pi = WF(i10) + 10 * i;
+        b.template st<3>(pi + 4, I.r0);
+        b.template st_from<1, 3>(pi + 6, I.r1);
+        b.template st_from<2, 3>(pi + 7, I.r2);
+        b.template st<3>(pi + 1, I.h);
+        pi[0] = m;
+        b.template st<3>(WF(f) + 6 * i, f.w);
+        b.template st<3>(WF(f) + 6 * i + 3, f.v);
+        if (own_type == DSIM_JOINT_REVOLUTE) {
+            float* S = WF(S) + 6 * tp.qk_ods;
+            b.template st<3>(S, s0.w);
+            b.template st<3>(S + 3, s0.v);
+        }
+    }
+}
+// fork_join_mid with a block fp that the side runs BEFORE it waits for the hand-over -- what it needs of the model constants and
+// of the state entering the phase, nothing the main block writes; fp's result is handed to fh.  An executor without the
+// three-block member (no helper wavefront: the host harness) runs fm, fp, fh one after the other.
+template <class Exec, class FM, class FP, class FH, class = void> struct DsimHasForkJoinMidPre : std::false_type {};
+template <class Exec, class FM, class FP, class FH>
+struct DsimHasForkJoinMidPre<Exec, FM, FP, FH, std::void_t<decltype(std::declval<Exec&>().fork_join_mid_pre(std::declval<FM&>(), std::declval<FP&>(), std::declval<FH&>()))>>
+    : std::true_type {};
+template <class Exec, class FM, class FP, class FH> DSIM_FN void dsim_fork_join_mid_pre(Exec& ex, FM&& fm, FP&& fp, FH&& fh) {
+    if constexpr (DsimHasForkJoinMidPre<Exec, FM, FP, FH>::value) ex.fork_join_mid_pre(fm, fp, fh);
+    else ex.fork_join_mid(fm, [&](int lane) { fh(lane, fp(lane)); });
+}
+// what a contact lane fetches before the poses are there: the contact's constants and its body
+struct DsimContactPre {
+    DsimContactConst cc;
+    int body;
+};
+template <class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics_walk_quad(const Ctx& c, Exec& ex, float* g_row) {
+    using D = decltype(c.d);
+    static_assert(DsimContactRegs<Ctx, Exec::NL>::value, "one contact per lane");
+    dsim_fork_join_mid_pre(ex, [&](int lane) {
+        const DsimTopoRegs& tp = ex.topo(lane);
+        if constexpr (DsimQuadKin<Ctx, Exec::NL>::QUAD) {
+            const DsimQuadLanes<Exec> b(ex, lane, tp.qc);
+            dsim_fk_quad_block(c, ex, b, tp);
+        } else {
+            const DsimQuadScalar b;
+            dsim_fk_quad_block(c, ex, b, tp);
+        }
+    }, [&](int lane) {
+        // The quad block behind the hand-over is shorter than the contacts: the side block does everything that does not read
+        // poses in front of its wait -- the head of the checkpoint row, (q, qd) entering the substep, and the contact constants
+        if (g_row) dsim_ckpt_store_row<Ctx, Exec::NL, 1>(c, lane, g_row);
+        DsimContactPre pre;
+        pre.cc = dsim_contact_load(c, lane < D::C ? lane : 0);
+        pre.body = ex.topo(lane).cbody_f;
+        return pre;
+    }, [&](int lane, const DsimContactPre& pre) {
+        if (lane < D::C) {
+            const v3 xp = ld3(WF(xsc) + 7 * pre.body);
+            const q4 xq = ldq(WF(xsc) + 7 * pre.body + 3);
+            const sv6 vb = ldsv(WF(v) + 6 * pre.body);
+            stsv(WF(cw) + 6 * lane, dsim_contact_wrench(pre.cc, xp, xq, vb));
+        }
+        dsim_fwd_contacts_per_body(c, ex, lane);
+    });
+}
+
 // g_row (one-phase dynamics only, DsimWaveDyn): the substep's checkpoint row -- its head (q, qd) is copied here, by the helper
 // wavefront where there is one, the rest beside the integrator (dsim_fwd_dynamics_wave)
 template <class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics(const Ctx& c, Exec& ex, float* g_row = nullptr) {
@@ -1335,6 +1532,10 @@ template <class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics(const Ctx& c, 
     }
     if constexpr (DsimScanFk<Ctx, Exec::NL>::value) {
         dsim_fwd_kinematics_scan(c, ex, g_row);
+        return;
+    }
+    if constexpr (DsimQuadKin<Ctx, Exec::NL>::value) {
+        dsim_fwd_kinematics_walk_quad(c, ex, g_row);
         return;
     }
     if constexpr (DsimContactsAfterWalk<Ctx, Exec::NL>::value) {

@@ -284,6 +284,12 @@ template <int NW, int PF = 6, int CW = 0, bool HELPER = false, int EPW = 1> stru
         static_assert(D >= 1 && D <= 15, "row shifts reach 1 .. 15 lanes");
         return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x110 + D, 0xf, 0xf, true));
     }
+    // component (P >> 2 c) & 3 of the lane's quad (lanes 4 k .. 4 k + 3) for c = lane & 3: a quad_perm DPP operand.  All four
+    // source lanes exist and are active wherever the phase code uses it (uniform control flow).
+    template <int P> __device__ __forceinline__ float quad_perm(float v) {
+        static_assert(P >= 0 && P <= 0xff, "quad_perm: four two-bit selectors");
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), P, 0xf, 0xf, true));
+    }
     // a_k += a_k[lane + D of the row] * w for six values at once: v_fmac_f32 with the DPP shift ON ITS OPERAND (the compiler
     // keeps a v_mov_b32_dpp + v_fmac pair for the builtin form: twice the instructions on a path where every issue slot counts).
     // A VGPR written by a VALU instruction may be read through DPP two wait states later at the earliest: the six lines are
@@ -394,6 +400,29 @@ template <int NW, int PF = 6, int CW = 0, bool HELPER = false, int EPW = 1> stru
         } else {
             fm(lane_());
             fh(lane_());
+            sync();
+        }
+    }
+    // ... and with a block fp that the helper runs BEFORE it waits for the hand-over (dsim_core.hpp: dsim_fork_join_mid_pre): fp
+    // reads only what was final at the barrier in front of the phase and returns what fh needs of it
+    template <class FM, class FP, class FH> __device__ __forceinline__ void fork_join_mid_pre(FM&& fm, FP&& fp, FH&& fh) {
+        if constexpr (HELPER) {
+            group_barrier();
+            if (helper_) {
+                const auto pre = fp(lane_());
+                stamp();          // (helper: fp is done; the next stamp is behind the hand-over barrier: the difference is waiting)
+                group_barrier();
+                stamp();
+                fh(lane_(), pre);
+            } else {
+                fm(lane_());
+            }
+            stamp();
+            group_barrier();
+            stamp();
+        } else {
+            fm(lane_());
+            fh(lane_(), fp(lane_()));
             sync();
         }
     }

@@ -1,0 +1,315 @@
+// dsim_math_quad.hpp -- component-per-lane ("quad") forms of the 3-vector / quaternion / spatial algebra of dsim_math.hpp.
+//
+// A link-level phase with one link per lane uses 9 of the 64 lanes of an Ant wavefront, and every lane runs its 3-, 4- and
+// 6-vector arithmetic as scalar structs.  A lone wavefront pays an issue slot per instruction whatever the instruction is, so the
+// phase gets shorter only with fewer instructions: here lanes 4 i .. 4 i + 3 hold the (x, y, z, w) components of link i's
+// values -- one float per lane -- and the component permutations of a cross product, a quaternion product or a matrix-vector
+// product are quad_perm DPP operands (dsim_quad_perm below).
+//
+// Every operation is written ONCE, over a backend B:
+//   DsimQuadLanes<Exec>  B::T = float, one component per lane; perm<P> is a quad_perm on the wavefront
+//   DsimQuadScalar       B::T = dq4 (four floats), one link per lane; perm<P> re-orders the struct's components
+// Both backends execute the same IEEE operations on every component in the same order -- the primitives are explicit
+// multiplies, adds and __builtin_fmaf with contraction off -- so the two layouts give bit-identical results.  The kernels with two
+// environments per wavefront (32 lanes; four lanes per link do not fit) run the scalar backend of the same phase source and
+// must match the one-environment kernels bit for bit (tests/test_gpu_parity.py).
+//
+// A 3-vector occupies components x, y, z; what its w component holds is unspecified (finite, never read by an xyz result).
+#pragma once
+#include <type_traits>
+#include <utility>
+
+// Component P & 3, (P >> 2) & 3, ... of the lane's QUAD (lanes 4 k .. 4 k + 3) into its lanes 0, 1, 2, 3: the device executor
+// has it as a quad_perm DPP operand (Exec::quad_perm<P>); an executor without that member (the host harness) goes through shfl.
+// All four lanes of a quad must call it together.
+template <class Exec, int P, class = void> struct DsimHasQuadPerm : std::false_type {};
+template <class Exec, int P>
+struct DsimHasQuadPerm<Exec, P, std::void_t<decltype(std::declval<Exec&>().template quad_perm<P>(0.f))>> : std::true_type {};
+template <int P, class Exec> DSIM_FN float dsim_quad_perm(Exec& ex, int lane, float v) {
+    if constexpr (DsimHasQuadPerm<Exec, P>::value) return ex.template quad_perm<P>(v);
+    else return ex.shfl(v, (lane & ~3) | ((P >> (2 * (lane & 3))) & 3));
+}
+
+#define DSIM_QP(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))   // quad_perm: component a -> x, b -> y, c -> z, d -> w
+enum {
+    DSIM_QP_XXXX = DSIM_QP(0, 0, 0, 0), DSIM_QP_YYYY = DSIM_QP(1, 1, 1, 1), DSIM_QP_ZZZZ = DSIM_QP(2, 2, 2, 2),
+    DSIM_QP_WWWW = DSIM_QP(3, 3, 3, 3),
+    DSIM_QP_YZXW = DSIM_QP(1, 2, 0, 3), DSIM_QP_ZXYW = DSIM_QP(2, 0, 1, 3),   // the two cyclic shifts of a cross product
+    DSIM_QP_XZYW = DSIM_QP(0, 2, 1, 3), DSIM_QP_ZYXW = DSIM_QP(2, 1, 0, 3), DSIM_QP_YXZW = DSIM_QP(1, 0, 2, 3),  // q x e_k
+    DSIM_QP_XYZX = DSIM_QP(0, 1, 2, 0), DSIM_QP_WWWX = DSIM_QP(3, 3, 3, 0),   // Hamilton product
+    DSIM_QP_YZXY = DSIM_QP(1, 2, 0, 1), DSIM_QP_ZXYY = DSIM_QP(2, 0, 1, 1),
+    DSIM_QP_ZXYZ = DSIM_QP(2, 0, 1, 2), DSIM_QP_YZXZ = DSIM_QP(1, 2, 0, 2)
+};
+
+// member functions (DSIM_FN is `static inline` on the host)
+#if defined(__HIPCC__)
+#define DSIM_MFN __device__ __forceinline__
+#else
+#define DSIM_MFN inline
+#endif
+
+struct dq4 {
+    float c[4];
+};
+
+// ---- scalar backend: one link per lane ---------------------------------------------------------------------------------------
+struct DsimQuadScalar {
+    typedef dq4 T;
+    static constexpr bool QUAD = false;
+    template <int P> DSIM_MFN T perm(T a) const { return T{{a.c[P & 3], a.c[(P >> 2) & 3], a.c[(P >> 4) & 3], a.c[(P >> 6) & 3]}}; }
+    DSIM_MFN T spl(float s) const { return T{{s, s, s, s}}; }
+    DSIM_MFN T lanes(float x, float y, float z, float w) const { return T{{x, y, z, w}}; }
+    DSIM_MFN T add(T a, T b) const {
+#pragma clang fp contract(off)
+        return T{{a.c[0] + b.c[0], a.c[1] + b.c[1], a.c[2] + b.c[2], a.c[3] + b.c[3]}};
+    }
+    DSIM_MFN T sub(T a, T b) const {
+#pragma clang fp contract(off)
+        return T{{a.c[0] - b.c[0], a.c[1] - b.c[1], a.c[2] - b.c[2], a.c[3] - b.c[3]}};
+    }
+    DSIM_MFN T mul(T a, T b) const {
+#pragma clang fp contract(off)
+        return T{{a.c[0] * b.c[0], a.c[1] * b.c[1], a.c[2] * b.c[2], a.c[3] * b.c[3]}};
+    }
+    DSIM_MFN T fma(T a, T b, T c) const {
+        return T{{__builtin_fmaf(a.c[0], b.c[0], c.c[0]), __builtin_fmaf(a.c[1], b.c[1], c.c[1]),
+                  __builtin_fmaf(a.c[2], b.c[2], c.c[2]), __builtin_fmaf(a.c[3], b.c[3], c.c[3])}};
+    }
+    DSIM_MFN T nfma(T a, T b, T c) const {   // c - a b
+        return T{{__builtin_fmaf(-a.c[0], b.c[0], c.c[0]), __builtin_fmaf(-a.c[1], b.c[1], c.c[1]),
+                  __builtin_fmaf(-a.c[2], b.c[2], c.c[2]), __builtin_fmaf(-a.c[3], b.c[3], c.c[3])}};
+    }
+    DSIM_MFN T sel_w(T a, T b) const { return T{{a.c[0], a.c[1], a.c[2], b.c[3]}}; }   // a's x, y, z with b's w
+    // components [0, N) from p[0 .. N); the others are 0
+    template <int N> DSIM_MFN T ld(const float* p) const {
+        T a{{0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+        for (int k = 0; k < N; ++k) a.c[k] = p[k];
+        return a;
+    }
+    // components [0, N) to p[0 .. N).  Stores of 3-vectors belong inside `if (b.xyz())` (the quad backend's w lane holds nothing)
+    template <int N> DSIM_MFN void st(float* p, T a) const {
+#pragma unroll
+        for (int k = 0; k < N; ++k) p[k] = a.c[k];
+    }
+    // components [N0, N) to p[N0 .. N)
+    template <int N0, int N> DSIM_MFN void st_from(float* p, T a) const {
+#pragma unroll
+        for (int k = N0; k < N; ++k) p[k] = a.c[k];
+    }
+    DSIM_MFN bool xyz() const { return true; }
+    // lane constants
+    DSIM_MFN T ex() const { return lanes(1.f, 0.f, 0.f, 0.f); }
+    DSIM_MFN T ey() const { return lanes(0.f, 1.f, 0.f, 0.f); }
+    DSIM_MFN T ez() const { return lanes(0.f, 0.f, 1.f, 0.f); }
+    DSIM_MFN T kx() const { return lanes(0.f, 1.f, -1.f, 0.f); }    // (q x e_x) = perm<XZY>(q) * kx
+    DSIM_MFN T ky() const { return lanes(-1.f, 0.f, 1.f, 0.f); }
+    DSIM_MFN T kz() const { return lanes(1.f, -1.f, 0.f, 0.f); }
+    DSIM_MFN T qs() const { return lanes(1.f, 1.f, 1.f, -1.f); }    // signs of the Hamilton product's second and third terms
+};
+
+// the lane constants of the quad backend, kept in registers for the whole launch (dsim_core.hpp: DsimTopoRegs)
+struct DsimQuadConsts {
+    float ex, ey, ez, kx, ky, kz, qs;
+};
+DSIM_FN void dsim_quad_consts_init(DsimQuadConsts& k, int lane) {
+    const int c = lane & 3;
+    k.ex = c == 0 ? 1.f : 0.f;
+    k.ey = c == 1 ? 1.f : 0.f;
+    k.ez = c == 2 ? 1.f : 0.f;
+    k.kx = c == 1 ? 1.f : c == 2 ? -1.f : 0.f;
+    k.ky = c == 0 ? -1.f : c == 2 ? 1.f : 0.f;
+    k.kz = c == 0 ? 1.f : c == 1 ? -1.f : 0.f;
+    k.qs = c == 3 ? -1.f : 1.f;
+}
+
+// ---- quad backend: one component per lane -------------------------------------------------------------------------------------
+template <class Exec> struct DsimQuadLanes {
+    typedef float T;
+    static constexpr bool QUAD = true;
+    Exec& e;
+    const int lane, c;   // c: this lane's component
+    const DsimQuadConsts& k;
+    DSIM_MFN DsimQuadLanes(Exec& e_, int lane_, const DsimQuadConsts& k_) : e(e_), lane(lane_), c(lane_ & 3), k(k_) {}
+    template <int P> DSIM_MFN T perm(T a) const { return dsim_quad_perm<P>(e, lane, a); }
+    DSIM_MFN T spl(float s) const { return s; }
+    DSIM_MFN T add(T a, T b) const {
+#pragma clang fp contract(off)
+        return a + b;
+    }
+    DSIM_MFN T sub(T a, T b) const {
+#pragma clang fp contract(off)
+        return a - b;
+    }
+    DSIM_MFN T mul(T a, T b) const {
+#pragma clang fp contract(off)
+        return a * b;
+    }
+    DSIM_MFN T fma(T a, T b, T cc) const { return __builtin_fmaf(a, b, cc); }
+    DSIM_MFN T nfma(T a, T b, T cc) const { return __builtin_fmaf(-a, b, cc); }
+    DSIM_MFN T sel_w(T a, T b) const { return c == 3 ? b : a; }
+    // lanes past the vector's last component re-read it: every address stays inside the vector
+    template <int N> DSIM_MFN T ld(const float* p) const { return p[c < N ? c : N - 1]; }
+    template <int N> DSIM_MFN void st(float* p, T a) const { p[c] = a; }
+    template <int N0, int N> DSIM_MFN void st_from(float* p, T a) const {
+        if (c >= N0) p[c] = a;
+    }
+    DSIM_MFN bool xyz() const { return c < 3; }
+    DSIM_MFN T ex() const { return k.ex; }
+    DSIM_MFN T ey() const { return k.ey; }
+    DSIM_MFN T ez() const { return k.ez; }
+    DSIM_MFN T kx() const { return k.kx; }
+    DSIM_MFN T ky() const { return k.ky; }
+    DSIM_MFN T kz() const { return k.kz; }
+    DSIM_MFN T qs() const { return k.qs; }
+};
+
+// ---- the operations, once for both backends ------------------------------------------------------------------------------------
+template <class B> struct DsimQuadSv {   // spatial vector (angular, linear)
+    typename B::T w, v;
+};
+template <class B> struct DsimQuadI {    // spatial inertia about the origin: A as three row vectors (A is symmetric up to rounding:
+    typename B::T r0, r1, r2, h;         // row i times x is used as column i), first moment h = m c
+    float m;
+};
+
+// On this target a quad_perm is free only as the operand of a multiply, an add or a subtract (VOP2 with a DPP source); in front of
+// an fma it is an instruction of its own.  The forms below are chosen for that: at most one permuted operand per instruction, products
+// whose result would need a permutation are kept in the rotated frame (dq_cross_t, dq_rotate) and permuted once, by the add or
+// multiply that consumes them.
+template <class B> DSIM_FN typename B::T dq_scale(const B& b, typename B::T a, float s) { return b.mul(a, b.spl(s)); }
+// a s + y
+template <class B> DSIM_FN typename B::T dq_axpy(const B& b, typename B::T a, float s, typename B::T y) { return b.fma(a, b.spl(s), y); }
+// t with a x b = perm<YZX>(t):  t = (c_z, c_x, c_y)
+template <class B> DSIM_FN typename B::T dq_cross_t(const B& b, typename B::T a, typename B::T x) {
+    return b.nfma(b.template perm<DSIM_QP_YZXW>(a), x, b.mul(a, b.template perm<DSIM_QP_YZXW>(x)));
+}
+// t + (a x b in the same rotated frame)
+template <class B> DSIM_FN typename B::T dq_cross_t_acc(const B& b, typename B::T t, typename B::T a, typename B::T x) {
+    return b.nfma(b.template perm<DSIM_QP_YZXW>(a), x, b.fma(a, b.template perm<DSIM_QP_YZXW>(x), t));
+}
+template <class B> DSIM_FN typename B::T dq_cross(const B& b, typename B::T a, typename B::T x) {
+    return b.template perm<DSIM_QP_YZXW>(dq_cross_t(b, a, x));
+}
+// acc + a x b, acc - a x b
+template <class B> DSIM_FN typename B::T dq_cross_acc(const B& b, typename B::T acc, typename B::T a, typename B::T x) {
+    return b.add(acc, b.template perm<DSIM_QP_YZXW>(dq_cross_t(b, a, x)));
+}
+template <class B> DSIM_FN typename B::T dq_cross_sub(const B& b, typename B::T acc, typename B::T a, typename B::T x) {
+    return b.sub(acc, b.template perm<DSIM_QP_YZXW>(dq_cross_t(b, a, x)));
+}
+// a . b of two 3-vectors in components x, y, z -- each component adds the three products in its own cyclic order, so the three
+// values may differ in the last bit; every one of them is a correctly formed dot product
+template <class B> DSIM_FN typename B::T dq_dot3(const B& b, typename B::T a, typename B::T x) {
+    const typename B::T p = b.mul(a, x);
+    return b.add(b.add(p, b.template perm<DSIM_QP_YZXW>(p)), b.template perm<DSIM_QP_ZXYW>(p));
+}
+// Hamilton product (dsim_math.hpp: qmul)
+template <class B> DSIM_FN typename B::T dq_qmul(const B& b, typename B::T a, typename B::T x) {
+    typename B::T r = b.mul(b.template perm<DSIM_QP_WWWW>(a), x);
+    r = b.fma(b.mul(b.template perm<DSIM_QP_XYZX>(a), b.qs()), b.template perm<DSIM_QP_WWWX>(x), r);
+    r = b.fma(b.mul(b.template perm<DSIM_QP_YZXY>(a), b.qs()), b.template perm<DSIM_QP_ZXYY>(x), r);
+    return b.nfma(b.template perm<DSIM_QP_ZXYZ>(a), b.template perm<DSIM_QP_YZXZ>(x), r);
+}
+// what the rotations by one quaternion share: 2 w, 2 w^2 - 1, the two cyclic shifts of q
+template <class B> struct DsimQuadRot {
+    typename B::T q, qy, q2z, tw, a;
+};
+template <class B> DSIM_FN DsimQuadRot<B> dq_rot_pre(const B& b, typename B::T q) {
+    DsimQuadRot<B> R;
+    const typename B::T qw = b.template perm<DSIM_QP_WWWW>(q), qz = b.template perm<DSIM_QP_ZXYW>(q);
+    R.q = q;
+    R.qy = b.template perm<DSIM_QP_YZXW>(q);
+    R.q2z = b.add(qz, qz);
+    R.tw = b.add(qw, qw);
+    R.a = b.fma(R.tw, qw, b.spl(-1.f));
+    return R;
+}
+// rotate(q, x) = x (2 w^2 - 1) + (qv x x) 2 w + qv 2 (qv . x), evaluated in the rotated frame (z, x, y) and permuted back at the end
+template <class B> DSIM_FN typename B::T dq_rotate(const B& b, const DsimQuadRot<B>& R, typename B::T x) {
+    typename B::T r = b.mul(b.template perm<DSIM_QP_ZXYW>(x), R.a);
+    const typename B::T t = b.nfma(R.qy, x, b.mul(R.q, b.template perm<DSIM_QP_YZXW>(x)));
+    r = b.fma(t, R.tw, r);
+    r = b.fma(R.q2z, dq_dot3(b, R.q, x), r);
+    return b.template perm<DSIM_QP_YZXW>(r);
+}
+template <class B> DSIM_FN typename B::T dq_rotate(const B& b, typename B::T q, typename B::T x) { return dq_rotate(b, dq_rot_pre(b, q), x); }
+// columns of the rotation matrix: rotate(q, e_x), rotate(q, e_y), rotate(q, e_z) without the terms that are exactly zero:
+// col_k = e_k (2 w^2 - 1) + (q x e_k) 2 w + q 2 q_k
+template <class B> DSIM_FN void dq_rot_cols(const B& b, const DsimQuadRot<B>& R, typename B::T& rx, typename B::T& ry, typename B::T& rz) {
+    const typename B::T qt = b.mul(R.q, R.tw), q2 = b.add(R.q, R.q);
+    rx = b.fma(R.q, b.template perm<DSIM_QP_XXXX>(q2), b.fma(b.ex(), R.a, b.mul(b.template perm<DSIM_QP_XZYW>(qt), b.kx())));
+    ry = b.fma(R.q, b.template perm<DSIM_QP_YYYY>(q2), b.fma(b.ey(), R.a, b.mul(b.template perm<DSIM_QP_ZYXW>(qt), b.ky())));
+    rz = b.fma(R.q, b.template perm<DSIM_QP_ZZZZ>(q2), b.fma(b.ez(), R.a, b.mul(b.template perm<DSIM_QP_YXZW>(qt), b.kz())));
+}
+// A x for A held as three row vectors, used as columns (A symmetric)
+template <class B> DSIM_FN typename B::T dq_sym_mul(const B& b, typename B::T r0, typename B::T r1, typename B::T r2, typename B::T x) {
+    typename B::T y = b.mul(b.template perm<DSIM_QP_XXXX>(x), r0);
+    y = b.fma(r1, b.template perm<DSIM_QP_YYYY>(x), y);
+    return b.fma(r2, b.template perm<DSIM_QP_ZZZZ>(x), y);
+}
+// world inertia about the origin of a body with COM cm, mass m, rotation columns (rx, ry, rz) and body-frame inertia
+// (ic0 .. ic5 = xx, xy, xz, yy, yz, zz):  Theta = R Ic R^T, A = Theta + m (c.c 1 - c c^T), h = m c
+template <class B>
+DSIM_FN DsimQuadI<B> dq_world_inertia(const B& b, typename B::T rx, typename B::T ry, typename B::T rz, typename B::T cm, float m,
+                                      float ic0, float ic1, float ic2, float ic3, float ic4, float ic5) {
+    typedef typename B::T T;
+    const T b0 = dq_axpy(b, rz, ic2, dq_axpy(b, ry, ic1, dq_scale(b, rx, ic0)));
+    const T b1 = dq_axpy(b, rz, ic4, dq_axpy(b, ry, ic3, dq_scale(b, rx, ic1)));
+    const T b2 = dq_axpy(b, rz, ic5, dq_axpy(b, ry, ic4, dq_scale(b, rx, ic2)));
+    DsimQuadI<B> I;
+    I.m = m;
+    I.h = dq_scale(b, cm, m);
+    const T mcc = dq_scale(b, dq_dot3(b, cm, cm), m);
+    I.r0 = b.fma(rz, b.template perm<DSIM_QP_XXXX>(b2), b.fma(ry, b.template perm<DSIM_QP_XXXX>(b1), b.mul(b.template perm<DSIM_QP_XXXX>(b0), rx)));
+    I.r1 = b.fma(rz, b.template perm<DSIM_QP_YYYY>(b2), b.fma(ry, b.template perm<DSIM_QP_YYYY>(b1), b.mul(b.template perm<DSIM_QP_YYYY>(b0), rx)));
+    I.r2 = b.fma(rz, b.template perm<DSIM_QP_ZZZZ>(b2), b.fma(ry, b.template perm<DSIM_QP_ZZZZ>(b1), b.mul(b.template perm<DSIM_QP_ZZZZ>(b0), rx)));
+    I.r0 = b.nfma(b.template perm<DSIM_QP_XXXX>(cm), I.h, b.fma(b.ex(), mcc, I.r0));
+    I.r1 = b.nfma(b.template perm<DSIM_QP_YYYY>(cm), I.h, b.fma(b.ey(), mcc, I.r1));
+    I.r2 = b.nfma(b.template perm<DSIM_QP_ZZZZ>(cm), I.h, b.fma(b.ez(), mcc, I.r2));
+    return I;
+}
+// I x = (A x.w + h x x.v, m x.v + x.w x h)
+template <class B> DSIM_FN DsimQuadSv<B> dq_inertia_mul(const B& b, const DsimQuadI<B>& I, const DsimQuadSv<B>& x) {
+    DsimQuadSv<B> y;
+    y.w = dq_cross_acc(b, dq_sym_mul(b, I.r0, I.r1, I.r2, x.w), I.h, x.v);
+    y.v = dq_cross_sub(b, dq_scale(b, x.v, I.m), I.h, x.w);
+    return y;
+}
+// acc + a x b for spatial motion vectors: (a.w x b.w, a.v x b.w + a.w x b.v)
+template <class B> DSIM_FN DsimQuadSv<B> dq_scross_acc(const B& b, const DsimQuadSv<B>& acc, const DsimQuadSv<B>& a, const DsimQuadSv<B>& x) {
+    DsimQuadSv<B> y;
+    y.w = dq_cross_acc(b, acc.w, a.w, x.w);
+    y.v = b.add(acc.v, b.template perm<DSIM_QP_YZXW>(dq_cross_t_acc(b, dq_cross_t(b, a.v, x.w), a.w, x.v)));
+    return y;
+}
+// acc + a x* b for a force vector b: (a.w x b.w + a.v x b.v, a.w x b.v)
+template <class B> DSIM_FN DsimQuadSv<B> dq_scross_dual_acc(const B& b, const DsimQuadSv<B>& acc, const DsimQuadSv<B>& a, const DsimQuadSv<B>& x) {
+    DsimQuadSv<B> y;
+    y.w = b.add(acc.w, b.template perm<DSIM_QP_YZXW>(dq_cross_t_acc(b, dq_cross_t(b, a.w, x.w), a.v, x.v)));
+    y.v = dq_cross_acc(b, acc.v, a.w, x.v);
+    return y;
+}
+// What the kinematics phase computes of a link behind its pose (rc, pc), twist v and bias acceleration a: COM, world inertia about
+// the origin and the body force  f = I a + v x* (I v) - (cm x m g, m g)
+template <class B> struct DsimQuadBody {
+    DsimQuadI<B> I;
+    DsimQuadSv<B> f;
+};
+template <class B>
+DSIM_FN DsimQuadBody<B> dq_body_inertia_force(const B& b, typename B::T rc, typename B::T pc, typename B::T com, typename B::T grav, float m,
+                                              float ic0, float ic1, float ic2, float ic3, float ic4, float ic5,
+                                              const DsimQuadSv<B>& a, const DsimQuadSv<B>& v) {
+    typedef typename B::T T;
+    const DsimQuadRot<B> R = dq_rot_pre(b, rc);
+    const T cm = b.add(dq_rotate(b, R, com), pc);
+    T rx, ry, rz;
+    dq_rot_cols(b, R, rx, ry, rz);
+    DsimQuadBody<B> r;
+    r.I = dq_world_inertia(b, rx, ry, rz, cm, m, ic0, ic1, ic2, ic3, ic4, ic5);
+    const DsimQuadSv<B> fb = dq_scross_dual_acc(b, dq_inertia_mul(b, r.I, a), v, dq_inertia_mul(b, r.I, v));
+    const T mg = dq_scale(b, grav, m);
+    r.f.w = dq_cross_acc(b, fb.w, mg, cm);
+    r.f.v = b.sub(fb.v, mg);
+    return r;
+}

@@ -5,8 +5,10 @@ active lanes (SQ_THREAD_CYCLES_VALU) into a flop rate instead of counting every 
     python tools/opcode_census.py [lib.so] [--out profiles/opcode_census.json]
 
 Disassembles the gfx950 code object of the library (llvm-objdump), and for every env-step kernel takes the instructions of its
-substep loop (the longest backward branch of the kernel: the loop over the substeps holds > 95 % of the dynamic instruction
-count -- 16 to 48 iterations against a prologue / epilogue executed once) and classifies them:
+substep loop (the backward branch of the kernel whose body holds the most floating-point VALU instructions: the loop over the
+substeps holds > 95 % of the dynamic instruction count -- 16 to 48 iterations against a prologue / epilogue executed once -- and
+all the per-substep arithmetic; the LONGEST loop is not it in every kernel: the env-step kernels' store / bookkeeping loop
+behind the substeps, v_readlane and global stores, is longer than the Ant substep loop) and classifies them:
 
     fma     v_fma / v_fmac / v_mac / v_mad / v_pk_fma (f32)      2 flop      (packed: x2)
     arith   v_mul / v_add / v_sub / v_pk_mul / v_pk_add (f32)    1 flop
@@ -74,8 +76,11 @@ def census(insts):
     for i, (addr, op, tgt) in enumerate(insts):
         if tgt is not None and base + tgt <= addr:   # backward branch: a loop
             j = next((k for k, x in enumerate(insts) if x[0] >= base + tgt), None)
-            if j is not None and (best is None or i - j > best[1] - best[0]):
-                best = (j, i)
+            if j is None:
+                continue
+            fp = sum(1 for _, o, _ in insts[j:i + 1] if FMA.match(o) or ARITH.match(o))
+            if best is None or (fp, i - j) > (best[2], best[1] - best[0]):   # (ties: the longer body)
+                best = (j, i, fp)
     body = insts[best[0]:best[1] + 1] if best else insts
     c = collections.Counter()
     for _, op, _ in body:

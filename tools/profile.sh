@@ -1,5 +1,5 @@
 #!/bin/bash
-# Runs on the GPU box (via gpurun): kernel trace + PMC passes of the default bench command.
+# Runs on the GPU box: kernel trace, then the PMC passes of the default bench command, each counter pass on its own (no tracing).
 # Writes small summaries to gpurun_out/prof_<tag>/ (raw CSVs stay in /tmp on the box).
 TAG=${1:-r02}
 ENVN=${2:-ant}
@@ -20,11 +20,11 @@ echo "$CMD" > $OUT/command.txt
 python -c "import sys; sys.path.insert(0, '$REPO'); import bench; print(bench.csrc_hash())" > $OUT/csrc_hash.txt 2>/dev/null
 run() { timeout 240 rocprofv3 --output-format csv "$@" < /dev/null; }
 run --kernel-trace --stats -d $RAW/trace -o t -- $CMD > $OUT/trace.log 2>&1
-run --pmc FETCH_SIZE --kernel-trace -d $RAW/fetch -o f -- $CMD > $OUT/fetch.log 2>&1
-run --pmc WRITE_SIZE --kernel-trace -d $RAW/write -o w -- $CMD > $OUT/write.log 2>&1
-run --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY --kernel-trace -d $RAW/sq -o s -- $CMD > $OUT/sq.log 2>&1
-run --pmc SQ_WAVES SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU --kernel-trace -d $RAW/sq3 -o s3 -- $CMD > $OUT/sq3.log 2>&1
-run --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE --kernel-trace -d $RAW/sq2 -o s2 -- $CMD > $OUT/sq2.log 2>&1
+run --pmc FETCH_SIZE -d $RAW/fetch -o f -- $CMD > $OUT/fetch.log 2>&1
+run --pmc WRITE_SIZE -d $RAW/write -o w -- $CMD > $OUT/write.log 2>&1
+run --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY -d $RAW/sq -o s -- $CMD > $OUT/sq.log 2>&1
+run --pmc SQ_WAVES SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU -d $RAW/sq3 -o s3 -- $CMD > $OUT/sq3.log 2>&1
+run --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR GRBM_GUI_ACTIVE -d $RAW/sq2 -o s2 -- $CMD > $OUT/sq2.log 2>&1
 find $RAW -type f -printf "%p %s\n" > $OUT/files.txt
 timeout 120 python - > $OUT/summary.txt 2>&1 < /dev/null <<PY
 import csv, glob, collections, os
