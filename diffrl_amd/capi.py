@@ -111,7 +111,7 @@ class DsimError(RuntimeError):
 
 
 _libs = {}
-EXPECTED_ABI = 108   # dsim_version() of the library this binding was written against (argument lists of include/dsim.h)
+EXPECTED_ABI = 109   # dsim_version() of the library this binding was written against (argument lists of include/dsim.h)
 
 
 def lib():
@@ -165,9 +165,12 @@ def load(path):
     L.dsim_body_transforms.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.dsim_body_kinematics.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
     L.dsim_body_kinematics_backward.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dsim_joint_dynamics.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.dsim_joint_dynamics_backward.argtypes = [vp, C.c_int] + [vp] * 12
     for fn in (L.dsim_model_create, L.dsim_model_destroy, L.dsim_step_forward, L.dsim_step_backward,
                L.dsim_env_step_forward, L.dsim_env_step_backward, L.dsim_env_observe, L.dsim_model_status,
-               L.dsim_body_transforms, L.dsim_body_kinematics, L.dsim_body_kinematics_backward):
+               L.dsim_body_transforms, L.dsim_body_kinematics, L.dsim_body_kinematics_backward, L.dsim_joint_dynamics,
+               L.dsim_joint_dynamics_backward):
         fn.restype = C.c_int
     _libs[path] = L
     return L
@@ -182,4 +185,5 @@ def check(rc, L=None):
 EXPORTS = ("dsim_last_error", "dsim_version", "dsim_model_create", "dsim_model_destroy", "dsim_model_variant", "dsim_model_device",
            "dsim_ckpt_floats", "dsim_ckpt_floats_mm", "dsim_model_set_ckpt_mode",
            "dsim_step_forward", "dsim_step_backward", "dsim_step_backward_literal", "dsim_literal_scratch_floats", "dsim_env_step_forward", "dsim_env_step_backward",
-           "dsim_env_observe", "dsim_model_status", "dsim_body_transforms", "dsim_body_kinematics", "dsim_body_kinematics_backward")
+           "dsim_env_observe", "dsim_model_status", "dsim_body_transforms", "dsim_body_kinematics", "dsim_body_kinematics_backward",
+           "dsim_joint_dynamics", "dsim_joint_dynamics_backward")

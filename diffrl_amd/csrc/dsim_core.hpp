@@ -2788,6 +2788,141 @@ DSIM_FN void dsim_body_kin_backward(const Ctx& c, Exec& ex, const float* g_q, co
     });
 }
 
+// Differentiable dynamic read-out of a given (q, qd, act, muscle_act) (dsim_joint_dynamics / dsim_joint_dynamics_backward,
+// include/dsim.h): the generalized forces tau [nd], the accelerations qdd [nd] = H(q)^-1 tau and the links' own world-frame
+// spatial forces f_s [L][6] (the reference's State.joint_tau / joint_qdd / body_f_s, model.py:378-388: inertial force minus
+// gravity plus the contacts and muscles acting on the link) -- ONE pass of the forward phases of a substep up to the solve, with
+// the mass matrix always built from the q handed in; no integration, no checkpoint, hence no step length.  The phases are the
+// step kernels' own (the composition of dsim_bwd_recompute_forward plus dsim_fwd_mass), so every kernel variant takes the
+// paths its step kernels take.  Null act / muscle_act mean zeros.
+template <bool ADJ, class Ctx, class Exec>
+DSIM_FN void dsim_joint_dyn_phases(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, const float* g_act,
+                                   const float* g_mact, int* g_status, int env) {
+    ex.begin_request();
+    ex.begin();
+    dsim_init_static(c, ex);
+    ex.run_both([&](int lane) { dsim_topo_init<ADJ>(c, ex, lane); });
+    ex.run([&](int lane) {
+        for (int k = lane; k < c.d.nq; k += Exec::NL) WF(q)[k] = g_q[k];
+        for (int k = lane; k < c.d.nd; k += Exec::NL) {
+            WF(qd)[k] = g_qd[k];
+            WF(act)[k] = g_act ? g_act[k] : 0.f;
+        }
+        for (int k = lane; k < c.d.M; k += Exec::NL) WF(mact)[k] = g_mact ? g_mact[k] : 0.f;
+    });
+    dsim_check_unit_quats(c, ex, g_status, env);
+    dsim_fwd_kinematics(c, ex);
+    dsim_fwd_external(c, ex);
+    dsim_fwd_tau(c, ex);
+    dsim_fwd_mass(c, ex);
+    dsim_fwd_solve(c, ex);
+}
+// f_s(i) is what the subtree sums f_tot add up (f_tot(i) = f_s(i) + the reference's ft_s(i), tests/ckpt_fields.py), read where
+// the variant's forward phases leave it: the body force f plus the body's contact wrenches (models without muscles: the
+// per-contact rows cw), f alone where the per-body gather of the muscle rows has added muscles and contacts to it, f plus the
+// per-body row cwb where that gather runs beside the kinematics (DsimWideOverlap).
+template <class Ctx, class Exec>
+DSIM_FN void dsim_joint_dyn_forward(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, const float* g_act,
+                                    const float* g_mact, float* g_tau, float* g_qdd, float* g_fs, int* g_status = nullptr,
+                                    int env = 0) {
+    dsim_joint_dyn_phases<false>(c, ex, g_q, g_qd, g_act, g_mact, g_status, env);
+    ex.run([&](int lane) {
+        for (int k = lane; k < c.d.nd; k += Exec::NL) {
+            if (g_tau) g_tau[k] = WF(tau)[k];
+            if (g_qdd) g_qdd[k] = WF(qdd)[k];
+        }
+        if (g_fs)
+            for (int it = lane; it < 6 * c.d.L; it += Exec::NL) {
+                const int i = it / 6, k = it - 6 * i;
+                float acc = WF(f)[it];
+                if constexpr (DsimWideOverlap<Ctx, Exec>::value) acc += WF(cwb)[it];
+                else if (c.d.NS == 0) acc = dsim_body_contact_sum(c, i, WF(cw), 6, k, acc);
+                g_fs[it] = acc;
+            }
+    });
+}
+// The reverse pass: cotangents (gtau, gqdd, gf_s), each possibly null (= zeros), to cotangents on (q, qd, act, muscle_act).  The
+// forward phases are re-run on the caller's inputs (nothing is kept between the calls), then
+//   1. adj qdd = gqdd;
+//   2. x = H^-1 adj qdd (H^-1 is symmetric), adj tau = x + gtau;
+//   3. adj H = -x qdd^T: the convention of the refresh substep (dsim_bwd_joint_space), for ONE solve the exact derivative;
+//   4. per dof, tau^T: PD target, limits, actuation (hinge: adj q, adj qd, adj act; ball: adj q, adj qd -- the ball joint's
+//      stiffness term acts on the vector part of its quaternion, and the component of that cotangent ALONG the quaternion is
+//      taken off, so that the quaternion blocks of gq are tangent as everywhere else) and adj S_d = -f_tot[link(d)] adj tau_d;
+//   5. adj f_s[j] = gf_s[j] - sum over the dofs d of the ancestors-or-self of j of S_d adj tau_d;
+//   6. dsim_bwd_mass;
+//   7. the body level this variant's step adjoint uses, entered with adj q / adj qd holding step 4's terms only.
+// In dsim_bwd_joint_space steps 2 - 5 are fused with the integrator's transpose (adj qdd = h adj qd'), which leaves a cotangent
+// that arrives on qdd or tau itself no entry point: hence this statement of them, on the general helpers.  x waits in prow (dead
+// behind the inversion).  The work arrays start as zeros (DsimImage::land), so adj act / adj muscle_act / the words of adj q and
+// adj qd that step 4 does not write are zeros when the body level accumulates into them.  Every output word is WRITTEN by the
+// lane that owns it: no atomics.
+template <class Ctx, class Exec>
+DSIM_FN void dsim_joint_dyn_backward(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, const float* g_act,
+                                     const float* g_mact, const float* g_gtau, const float* g_gqdd, const float* g_gfs,
+                                     float* g_gq, float* g_gqd, float* g_gact, float* g_gmact) {
+    const int nd = c.d.nd;
+    dsim_joint_dyn_phases<true>(c, ex, g_q, g_qd, g_act, g_mact, nullptr, 0);
+    ex.run([&](int lane) {
+        for (int d = lane; d < nd; d += Exec::NL) WF(aqdd)[d] = g_gqdd ? g_gqdd[d] : 0.f;
+    });
+    ex.run([&](int lane) {
+        for (int i = lane; i < nd; i += Exec::NL) {
+            const float x = dsim_dot_n(WF(hinv) + i * nd, WF(aqdd), nd);
+            WF(prow)[i] = x;
+            WF(atau)[i] = x + (g_gtau ? g_gtau[i] : 0.f);
+        }
+    });
+    ex.run([&](int lane) {
+        for (int it = lane; it < nd * nd; it += Exec::NL) {
+            const int i = it / nd, j = it - nd * i;
+            WF(aH)[it] = 0.f - WF(prow)[i] * WF(qdd)[j];
+        }
+        for (int d = lane; d < nd; d += Exec::NL) {
+            const int i = CI(dof_link)[d], type = CI(jtype)[i], cs = CI(qstart)[i], ds = CI(qdstart)[i];
+            const float at = WF(atau)[d];
+            const float tke = CF(tke)[i], tkd = CF(tkd)[i], lke = CF(lke)[i], lkd = CF(lkd)[i];
+            stsv(WF(aS) + 6 * d, ldsv(WF(ftot) + 6 * i) * (-at));
+            if (type == DSIM_JOINT_PRISMATIC || type == DSIM_JOINT_REVOLUTE) {
+                const float q = WF(q)[cs];
+                float dq = -tke;
+                if (q < CF(lower)[cs]) dq = -tke - lke;
+                if (q > CF(upper)[cs]) dq = -tke - lke;
+                WF(aq)[cs] = dq * at;
+                WF(aqd)[d] = (-tkd - lkd) * at;
+                WF(aact)[d] = at;
+            } else if (type == DSIM_JOINT_BALL) {
+                const int k = d - ds;
+                const q4 r = ldq(WF(q) + cs);
+                const v3 g = ld3(WF(atau) + ds) * (-tke);
+                const float rad = g.x * r.x + g.y * r.y + g.z * r.z;   // (g, 0) . r
+                WF(aq)[cs + k] = (-tke) * at - rad * WF(q)[cs + k];
+                if (k == 0) WF(aq)[cs + 3] = 0.f - rad * r.w;
+                WF(aqd)[d] = (-tkd) * at;
+            }
+        }
+        for (int it = Exec::NL - 1 - lane; it < 6 * c.d.L; it += Exec::NL) {
+            const int j = it / 6, k = it - 6 * j;
+            float acc = g_gfs ? g_gfs[it] : 0.f;
+            const dsim_int_a* lst = CI(adof_list);
+            for (int e = CI(adof_start)[j]; e < CI(adof_start)[j + 1]; ++e) acc -= WF(S)[6 * lst[e] + k] * WF(atau)[lst[e]];
+            WF(af)[it] = acc;
+        }
+    });
+    dsim_bwd_mass(c, ex);
+    if constexpr (DsimRowTree<Ctx, Exec>::value) dsim_bwd_bodies_rowtree(c, ex, true);
+    else dsim_bwd_bodies(c, ex, true);
+    ex.run([&](int lane) {
+        for (int k = lane; k < c.d.nq; k += Exec::NL) g_gq[k] = WF(aq)[k];
+        for (int k = lane; k < nd; k += Exec::NL) {
+            g_gqd[k] = WF(aqd)[k];
+            if (g_gact) g_gact[k] = WF(aact)[k];
+        }
+        if (g_gmact)
+            for (int k = lane; k < c.d.M; k += Exec::NL) g_gmact[k] = WF(amact)[k];
+    });
+}
+
 // ================================================================================================
 // adjoint (hand-derived reverse sweep of one substep)
 // ================================================================================================

@@ -930,6 +930,41 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_body_kin_bwd_kernel(KCommon
 }
 
 
+// Differentiable dynamic read-out (dsim_core.hpp: dsim_joint_dyn_forward / dsim_joint_dyn_backward): one environment per
+// workgroup, plain launch mode.  The forward kernel needs the forward image only; the adjoint re-runs the forward phases and
+// goes on with the mass-matrix and body-level phases of the step adjoint on the adjoint image.
+template <class O, class D, int NW>
+__global__ __launch_bounds__(DSIM_NL * NW) void dsim_joint_dyn_kernel(KCommonT<O, D> k, const float* __restrict__ q,
+                                                                    const float* __restrict__ qd, const float* __restrict__ act,
+                                                                    const float* __restrict__ mact, float* tau, float* qdd, float* fs) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, 6, dsim_const_words<O>(), false> ex;
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex);
+    const size_t nq = k.d.nq, nd = k.d.nd, M = k.d.M, L = k.d.L;
+    dsim_joint_dyn_forward(c, ex, q + e * nq, qd + e * nd, act ? act + e * nd : nullptr, (mact && M) ? mact + e * M : nullptr,
+                           tau ? tau + e * nd : nullptr, qdd ? qdd + e * nd : nullptr, fs ? fs + e * 6 * L : nullptr, k.status, e);
+}
+
+template <class O, class D, int NW>
+__global__ __launch_bounds__(DSIM_NL * NW) void dsim_joint_dyn_bwd_kernel(KCommonT<O, D> k, const float* __restrict__ q,
+                                                                        const float* __restrict__ qd, const float* __restrict__ act,
+                                                                        const float* __restrict__ mact, const float* __restrict__ gtau,
+                                                                        const float* __restrict__ gqdd, const float* __restrict__ gfs,
+                                                                        float* gq, float* gqd, float* gact, float* gmact) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, 6, dsim_const_words<O>(), false> ex;
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    const size_t nq = k.d.nq, nd = k.d.nd, M = k.d.M, L = k.d.L;
+    dsim_joint_dyn_backward(c, ex, q + e * nq, qd + e * nd, act ? act + e * nd : nullptr, (mact && M) ? mact + e * M : nullptr,
+                            gtau ? gtau + e * nd : nullptr, gqdd ? gqdd + e * nd : nullptr, gfs ? gfs + e * 6 * L : nullptr,
+                            gq + e * nq, gqd + e * nd, gact ? gact + e * nd : nullptr, (gmact && M) ? gmact + e * M : nullptr);
+}
+
+
 thread_local std::string g_err;
 
 int fail(int code, const std::string& msg) {
@@ -1193,7 +1228,7 @@ int make_spec(const dsim_model* m, const dsim_env_spec* e, DsimEnvSpec& sp) {
 extern "C" {
 
 const char* dsim_last_error(void) { return g_err.c_str(); }
-int dsim_version(void) { return 108; }
+int dsim_version(void) { return 109; }
 
 int dsim_model_create(const dsim_model_desc* desc, dsim_model** out) {
     if (!desc || !out) return fail(DSIM_ERR_INVALID, "null argument");
@@ -1248,6 +1283,12 @@ int dsim_model_create(const dsim_model_desc* desc, dsim_model** out) {
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e == hipSuccess)
                 e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_body_kin_bwd_kernel<O, D, NW>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_joint_dyn_kernel<O, D, NW>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_joint_dyn_bwd_kernel<O, D, NW>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             return 0;
         });
@@ -1499,6 +1540,39 @@ int dsim_body_kinematics_backward(const dsim_model* m, int n_envs, const float* 
         hipLaunchKernelGGL((dsim_body_kin_bwd_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
                            (size_t)m->lay.o.total_words * 4, st, k, q, qd, gX_sc, gX_sm, gv_s, gq, gqd);
         return launched("launch dsim_body_kin_bwd_kernel");
+    });
+}
+
+int dsim_joint_dynamics(const dsim_model* m, int n_envs, const float* q, const float* qd, const float* act, const float* muscle_act,
+                        float* tau, float* qdd, float* f_s, void* hip_stream) {
+    int rc = check_common(m, n_envs, 1.0f, 1, 1);
+    if (rc) return rc;
+    if (!q || !qd) return fail(DSIM_ERR_INVALID, "null pointer");
+    if (!tau && !qdd && !f_s) return fail(DSIM_ERR_INVALID, "no output: tau, qdd and f_s are all null");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return dispatch(m, [&](auto o, auto d, auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
+        hipLaunchKernelGGL((dsim_joint_dyn_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
+                           (size_t)m->lay.o.fwd_words * 4, st, k, q, qd, act, muscle_act, tau, qdd, f_s);
+        return launched("launch dsim_joint_dyn_kernel");
+    });
+}
+
+int dsim_joint_dynamics_backward(const dsim_model* m, int n_envs, const float* q, const float* qd, const float* act,
+                                 const float* muscle_act, const float* gtau, const float* gqdd, const float* gf_s, float* gq,
+                                 float* gqd, float* gact, float* gmuscle_act, void* hip_stream) {
+    int rc = check_common(m, n_envs, 1.0f, 1, 1);
+    if (rc) return rc;
+    if (!q || !qd || !gq || !gqd) return fail(DSIM_ERR_INVALID, "null pointer");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return dispatch(m, [&](auto o, auto d, auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
+        k.status = nullptr;   // the forward launch checked the state
+        hipLaunchKernelGGL((dsim_joint_dyn_bwd_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
+                           (size_t)m->lay.o.total_words * 4, st, k, q, qd, act, muscle_act, gtau, gqdd, gf_s, gq, gqd, gact, gmuscle_act);
+        return launched("launch dsim_joint_dyn_bwd_kernel");
     });
 }
 

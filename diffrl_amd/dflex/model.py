@@ -459,5 +459,16 @@ class Model:
         These are the frames of the state handed in; State.body_X_sc keeps the reference's one-substep lag and no grad_fn."""
         return self.engine().body_kinematics(state.joint_q, state.joint_qd)
 
+    def joint_dynamics(self, state, joint_act=None, muscle_activation=None):
+        """(joint_tau, joint_qdd, body_f_s) of state.joint_q / joint_qd under the given actuation, shaped like the reference's
+        State tensors ([joint_dof_count], [joint_dof_count], [link_count, 6]) and DIFFERENTIABLE in the state and the actuation
+        (Engine.joint_dynamics): torque, acceleration and link-force terms of a loss back-propagate into the joint state, the
+        actions and, through the step that produced the state, further back.  joint_act defaults to state.joint_act and
+        muscle_activation to model.muscle_activation; on the fused env path, which keeps no joint_act tensor, pass the joint_act
+        to evaluate.  The mass matrix is that of the state handed in."""
+        act = joint_act if joint_act is not None else getattr(state, "joint_act", None)
+        mact = muscle_activation if muscle_activation is not None else getattr(self, "muscle_activation", None)
+        return self.engine().joint_dynamics(state.joint_q, state.joint_qd, act, mact if self.muscle_count > 0 else None)
+
     def flatten(self):
         return [v for v in self.__dict__.values() if torch.is_tensor(v)]

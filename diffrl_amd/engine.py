@@ -168,6 +168,59 @@ class Engine:
                                                                _ptr(gq), _ptr(gqd), st))
         return gq, gqd
 
+    def joint_dynamics(self, q, qd, act=None, muscle_act=None):
+        """(tau [n_envs * n_qd], qdd [n_envs * n_qd], f_s [n_envs * n_links, 6]): the generalized force applied (PD target, joint
+        limits and actuation included), the joint accelerations H(q)^-1 tau and every link's own world-frame spatial force
+        (inertial force minus gravity plus its ground contacts and muscles) -- the reference's State.joint_tau / joint_qdd /
+        body_f_s -- of the state and actuation HANDED IN, differentiable in all four inputs (JointDynamics below; one launch
+        forward, one backward).  act / muscle_act default to zeros.  No step length enters: nothing is integrated."""
+        return JointDynamics.apply(self, q, qd, act, muscle_act)
+
+    def joint_dynamics_forward(self, q, qd, act=None, muscle_act=None):
+        """dsim_joint_dynamics on detached contiguous tensors"""
+        n = self._dyn_check(q, qd, act, muscle_act)
+        L = self.template.n_links
+        tau = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
+        qdd = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
+        fs = torch.empty((n * L, 6), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self._ck(self._lib.dsim_joint_dynamics(self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(muscle_act), _ptr(tau), _ptr(qdd),
+                                                   _ptr(fs), st))
+        return tau, qdd, fs
+
+    def joint_dynamics_backward(self, q, qd, act, muscle_act, gtau, gqdd, gfs):
+        """dsim_joint_dynamics_backward: any cotangent may be None (= zeros, no buffer); -> (gq, gqd, gact, gmuscle_act | None), flat"""
+        n = self._dyn_check(q, qd, act, muscle_act)
+        L, M = self.template.n_links, self.template.n_muscles
+        for g, size, name in ((gtau, n * self.n_qd, "gtau"), (gqdd, n * self.n_qd, "gqdd"), (gfs, n * L * 6, "gf_s")):
+            if g is not None:
+                self._check(g, 1, name)
+                if g.numel() != size:
+                    raise capi.DsimError("%s has the wrong size" % name)
+        gq = torch.empty(n * self.n_q, dtype=torch.float32, device=self.device)
+        gqd = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
+        gact = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
+        gmact = torch.empty(n * M, dtype=torch.float32, device=self.device) if M > 0 else None
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self._ck(self._lib.dsim_joint_dynamics_backward(self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(muscle_act), _ptr(gtau),
+                                                            _ptr(gqdd), _ptr(gfs), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gmact), st))
+        return gq, gqd, gact, gmact
+
+    def _dyn_check(self, q, qd, act, muscle_act):
+        self._check(q, self.n_q, "joint_q")
+        self._check(qd, self.n_qd, "joint_qd")
+        n = q.numel() // self.n_q
+        M = self.template.n_muscles
+        for t, cols, name in ((qd, self.n_qd, "joint_qd"), (act, self.n_qd, "joint_act"), (muscle_act, M, "muscle_activation")):
+            if t is None or (t is muscle_act and M == 0):
+                continue
+            self._check(t, cols, name)
+            if t.numel() != n * cols:
+                raise capi.DsimError("state tensors disagree on the number of environments")
+        return n
+
     def last_substep_q(self, ckpt, substeps):
         """joint_q ENTERING the last substep of the step that wrote `ckpt` (the head of that substep's checkpoint row): what the
         reference's eval_rigid_fk saw when it filled the returned State's body_X_sc (sim.py:2316-2601)."""
@@ -395,6 +448,36 @@ class BodyKinematics(torch.autograd.Function):
         c = lambda g: g.contiguous() if g is not None else None  # noqa: E731
         gq, gqd = ctx.engine.body_kinematics_backward(q, qd if ctx.has_qd else None, c(gxsc), c(gxsm), c(gvs))
         return None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]) if ctx.has_qd else None
+
+
+class JointDynamics(torch.autograd.Function):
+    """(joint_q, joint_qd, joint_act | None, muscle_activation | None) -> (tau, qdd, f_s): the dynamic read-out of a state with
+    its adjoint (dsim_joint_dynamics / dsim_joint_dynamics_backward); the backward launch re-runs the forward pass on the saved
+    inputs.  The quaternion blocks of the returned joint_q gradient have no component along the quaternion, as SimStep's."""
+
+    @staticmethod
+    def forward(ctx, engine, q, qd, act, mact):
+        M = engine.template.n_muscles
+        det = lambda t: t.detach().contiguous() if t is not None else None  # noqa: E731
+        qc, qdc, ac, mc = det(q), det(qd), det(act), det(mact) if M > 0 else None
+        tau, qdd, fs = engine.joint_dynamics_forward(qc, qdc, ac, mc)
+        ctx.engine = engine
+        ctx.has = (ac is not None, mc is not None)
+        ctx.shapes = (q.shape, qd.shape, act.shape if act is not None else None, mact.shape if mact is not None else None)
+        ctx.set_materialize_grads(False)   # an output the loss does not read costs no cotangent buffer
+        ctx.save_for_backward(qc, qdc, ac if ac is not None else qc.new_empty(0), mc if mc is not None else qc.new_empty(0))
+        return tau, qdd, fs
+
+    @staticmethod
+    def backward(ctx, gtau, gqdd, gfs):
+        if gtau is None and gqdd is None and gfs is None:
+            return None, None, None, None, None
+        q, qd, act, mact = ctx.saved_tensors
+        c = lambda g: g.contiguous() if g is not None else None  # noqa: E731
+        gq, gqd, gact, gmact = ctx.engine.joint_dynamics_backward(q, qd, act if ctx.has[0] else None, mact if ctx.has[1] else None,
+                                                                  c(gtau), c(gqdd), c(gfs))
+        return (None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), gact.view(ctx.shapes[2]) if ctx.has[0] else None,
+                gmact.view(ctx.shapes[3]) if ctx.has[1] else None)
 
 
 class SimStep(torch.autograd.Function):

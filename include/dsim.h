@@ -219,6 +219,33 @@ int dsim_body_kinematics_backward(const dsim_model* m, int n_envs, const float* 
                                   const float* gX_sc, const float* gX_sm, const float* gv_s /* each may be NULL = zeros */,
                                   float* gq, float* gqd /* NULL iff qd is NULL */, void* hip_stream);
 
+/* Differentiable joint dynamics: generalized forces, accelerations and link forces of a given state, and the reverse pass.
+ *   tau [N][nd]     the generalized force applied (the reference's State.joint_tau): -S . f_tot plus PD target, joint limits
+ *                   and actuation;
+ *   qdd [N][nd]     H(q)^-1 tau, the mass matrix ALWAYS built from the q handed in (State.joint_qdd of a refresh substep);
+ *   f_s [N][L][6]   every link's OWN world-frame spatial force (torque about the world origin, force), the reference's
+ *                   State.body_f_s: inertial force minus gravity, plus the ground contacts and muscles acting on the link.
+ * One pass of the forward phases of a substep up to the solve: nothing is integrated, so there is no step length.  act and
+ * muscle_act may be NULL (= zeros); each output may be NULL (skipped), not all three.
+ * The backward call maps cotangents on the three tensors (each may be NULL = zeros) to cotangents on q, qd, act and muscle_act,
+ * which are WRITTEN, not accumulated (gact and gmuscle_act may be NULL).  It re-runs the forward pass on (q, qd, act,
+ * muscle_act): nothing is kept between the two calls.  Adjoint steps: adj qdd = gqdd; adj tau = H^-1 adj qdd + gtau; the
+ * mass-matrix cotangent in the convention of the refresh substep above, dH = -(L L^T)^-1 g_qdd qdd^T (for one solve the exact
+ * derivative); the per-dof adjoint of tau; gf_s added to the cotangent of the link's own force; then the mass-matrix and body
+ * levels of the step adjoint.  Pose cotangents are world-frame wrenches: the quaternion blocks of gq have
+ * NO component along the quaternion -- project the reference's literal gradient onto the tangent space before comparing.
+ * Like every call here: device pointers borrowed for the call, launches on the caller's stream, no host synchronisation,
+ * deterministic (no atomics).  Precondition: unit quaternions in q; the forward call checks it like the step functions do (the
+ * NEXT call on the model returns DSIM_ERR_INVALID), the backward call does not check again. */
+int dsim_joint_dynamics(const dsim_model* m, int n_envs, const float* q, const float* qd,
+                        const float* act /* NULL = zeros */, const float* muscle_act /* NULL = zeros */,
+                        float* tau, float* qdd, float* f_s /* each may be NULL, not all three */, void* hip_stream);
+int dsim_joint_dynamics_backward(const dsim_model* m, int n_envs, const float* q, const float* qd,
+                                 const float* act, const float* muscle_act,
+                                 const float* gtau, const float* gqdd, const float* gf_s /* each may be NULL = zeros */,
+                                 float* gq, float* gqd, float* gact /* may be NULL */, float* gmuscle_act /* may be NULL */,
+                                 void* hip_stream);
+
 /* ---- fused environment surface -------------------------------------
  * The per-step torch glue of the reference environments -- action clip + scale into joint_act /
  * muscle activations (envs/ant.py:157-163, humanoid.py:188-211, snu_humanoid.py:245-271,

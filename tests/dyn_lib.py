@@ -1,0 +1,190 @@
+"""Test infrastructure of the differentiable joint dynamics (dsim_joint_dynamics / dsim_joint_dynamics_backward):
+
+* the lane-serial host build of the new phase code (tests/emu/dsim_emu_dyn.cpp), compiled here with the flags of
+  tests/emu/Makefile, for the shipped layouts and for the two user models of tests/golden/user_*.npz;
+* the bounds of the adjoint comparison against tests/golden/<env>_dyn.npz (tools/gen_dynamics_golden.py), shared by the host
+  and the GPU tier.
+
+Bounds.  The reference's own gradient moves when its inputs move by 1 ulp; the fixtures record that noise per state and tensor
+for EACH of the four cotangent sets (noise_<t>[B] for all three cotangents together, noise_<t>_<set>[B] for tau, qdd, fs alone),
+each on the scale of that set's own reference tensor: the three single-cotangent gradients are parts of a sum and cancel, so a
+part's noise relative to its own size is not the sum's (CartPole, cotangent on qdd alone: the reference leaves 2.4e-4 in the
+cart-position column of gq, whose exact value is 0, next to a largest entry of 24; its recorded noise there is 5.6e-5 against
+1.2e-6 for the sum).  Every set is compared in ITS OWN max-norm.  The kernels associate their sums differently from the reference,
+which acts like a few ulp of input noise, so the bound per (model, set, tensor) is FACTOR = 10 x that set's recorded noise (the
+max over the compared states), never below FLOOR = 1e-5 (the bound of the kinematic adjoint) and never above CEIL = 1e-3 (the
+step-gradient bound of tests/test_gpu_parity.py).  A (state, tensor) pair whose recorded noise in a set exceeds EXCLUDE = 3e-4
+-- a third of the ceiling, so that reference noise plus our own still fits -- is not compared in that set (it must still be
+finite); over all sets at most three (state, tensor) pairs may be excluded, all of them SNUHumanoid joint_q gradients (its states
+0 - 2 sit on a joint-limit / contact switch: 1.6e-3 .. 2.3e-2 wherever tau or qdd carry a cotangent; with the cotangent on f_s
+alone they are quiet and compared).
+"""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+from diffrl_amd.capi import make_desc
+from kin_lib import CXXFLAGS, ENVS, USER_MODELS, waves_of  # noqa: F401
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EMU_DIR = os.path.join(ROOT, "tests", "emu")
+CSRC = os.path.join(ROOT, "diffrl_amd", "csrc")
+FACTOR, FLOOR, CEIL, EXCLUDE = 10.0, 1e-5, 1e-3, 3e-4
+MAX_EXCLUDED = {"snu": 3}          # pairs (state, gq); every other model: none
+FWD_BOUND = 1e-4                   # forces and accelerations of one substep (tests/ckpt_fields.py BOUNDS)
+RADIAL = 1e-6
+COTANGENTS = ("tau", "qdd", "fs", "all")
+# Cross-check of the qdd adjoint against dsim_step_backward of one substep (tests/test_joint_dynamics_cpu.py): the largest
+# disagreement measured on the host harness over the six shipped models, generic and specialised, where both sides are pinned to
+# the reference -- CartPole gq 1.48e-5 (its gradient is the remainder of cancelling stiffness terms; SNUHumanoid gmact 1.2e-5,
+# Humanoid 1.1e-5, the others <= 2.3e-6) -- times 10, floor 1e-5.  The two user models sit at <= 2.8e-5 on the host.
+CHECK_MEASURED = 1.48e-5
+CHECK_BOUND = max(10 * CHECK_MEASURED, 1e-5)
+CHECK_H = 1.0 / 960.0
+_libs = {}
+
+
+def _sources():
+    return [os.path.join(EMU_DIR, f) for f in ("dsim_emu_dyn.cpp", "dsim_emu.cpp")] + \
+           [os.path.join(CSRC, f) for f in ("dsim_core.hpp", "dsim_math.hpp", "dsim_layout.hpp", "dsim_static_layouts.hpp",
+                                            "dsim_literal.hpp")] + [os.path.join(ROOT, "include", "dsim.h")]
+
+
+def dyn_emu(user=False):
+    """the host harness with the dynamics entry points: shipped layouts, or (user) those of the two user models"""
+    if user in _libs:
+        return _libs[user]
+    so = os.path.join(EMU_DIR, "libdsim_emu_dyn_user.so" if user else "libdsim_emu_dyn.so")
+    deps = _sources() + ([p for _, p in USER_MODELS] + [os.path.join(ROOT, "diffrl_amd", "specialise.py")] if user else [])
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        tmp = so + ".tmp%d" % os.getpid()
+        cmd = ["g++"] + CXXFLAGS
+        with tempfile.TemporaryDirectory() as d:
+            if user:
+                from diffrl_amd import specialise
+                from diffrl_amd.template import ArticulationTemplate
+                hdr = os.path.join(d, "dyn_user_layouts.hpp")
+                with open(hdr, "w") as f:
+                    f.write(specialise.render([(tag, ArticulationTemplate.load(p)) for tag, p in USER_MODELS]))
+                cmd += ['-DDSIM_STATIC_LAYOUTS_FILE="%s"' % hdr, "-DDSIM_STATIC_VARIANTS(X)=" + " ".join("X(%s)" % t for t, _ in USER_MODELS)]
+            subprocess.check_call(cmd + ["-shared", "-o", tmp, os.path.join(EMU_DIR, "dsim_emu_dyn.cpp")])
+        os.replace(tmp, so)
+    _libs[user] = C.CDLL(so)
+    return _libs[user]
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+def _c(a):
+    return np.ascontiguousarray(a, dtype=np.float32) if a is not None else None
+
+
+def _mode(lib, static, waves):
+    lib.dsim_emu_use_static(1 if static else 0)
+    lib.dsim_emu_set_waves(waves)
+
+
+def emu_dyn_forward(t, q, qd, act, mact, static=False, waves=1, user=False):
+    lib = dyn_emu(user)
+    desc, keep = make_desc(t)
+    q, qd, act, mact = _c(q), _c(qd), _c(act), _c(mact)
+    N, L = q.shape[0], t.n_links
+    tau = np.full((N, t.n_qd), np.nan, np.float32)
+    qdd = np.full((N, t.n_qd), np.nan, np.float32)
+    fs = np.full((N, L, 6), np.nan, np.float32)
+    _mode(lib, static, waves)
+    rc = lib.dsim_emu_joint_dynamics(C.byref(desc), C.c_int(N), _p(q), _p(qd), _p(act), _p(mact), _p(tau), _p(qdd), _p(fs))
+    _mode(lib, False, 1)
+    assert rc == 0, rc
+    return tau, qdd, fs
+
+
+def emu_dyn_backward(t, q, qd, act, mact, gtau, gqdd, gfs, static=False, waves=1, user=False):
+    """-> gq, gqd, gact, gmact (None for a model without muscles)"""
+    lib = dyn_emu(user)
+    desc, keep = make_desc(t)
+    q, qd, act, mact, gtau, gqdd, gfs = _c(q), _c(qd), _c(act), _c(mact), _c(gtau), _c(gqdd), _c(gfs)
+    N = q.shape[0]
+    gq = np.full((N, t.n_q), np.nan, np.float32)
+    gqd = np.full((N, t.n_qd), np.nan, np.float32)
+    gact = np.full((N, t.n_qd), np.nan, np.float32)
+    gmact = np.full((N, t.n_muscles), np.nan, np.float32) if t.n_muscles else None
+    _mode(lib, static, waves)
+    rc = lib.dsim_emu_joint_dynamics_backward(C.byref(desc), C.c_int(N), _p(q), _p(qd), _p(act), _p(mact), _p(gtau), _p(gqdd),
+                                              _p(gfs), _p(gq), _p(gqd), _p(gact), _p(gmact))
+    _mode(lib, False, 1)
+    assert rc == 0, rc
+    return gq, gqd, gact, gmact
+
+
+def emu_step_adjoint(t, q, qd, act, mact, h, gqd_out, static=False, waves=1, user=False):
+    """dsim_step_backward of ONE substep of length h with a fresh mass matrix on the host harness, gq_out = 0:
+    gq_in = h (d qdd / d q)^T g, gact = h (d qdd / d act)^T g (and gmact likewise) -> (gq_in, gact, gmact | None)"""
+    lib = dyn_emu(user)
+    desc, keep = make_desc(t)
+    q, qd, act, gqd_out = _c(q), _c(qd), _c(act), _c(gqd_out)
+    N = q.shape[0]
+    m = _c(mact) if (mact is not None and t.n_muscles) else np.zeros((N, 0), np.float32)
+    _mode(lib, static, waves)
+    lib.dsim_emu_ckpt_floats.restype = C.c_longlong
+    ck = np.zeros((N, int(lib.dsim_emu_ckpt_floats(C.byref(desc), C.c_int(1), C.c_int(1)))), np.float32)
+    qo, qdo = np.zeros_like(q), np.zeros_like(qd)
+    rc = lib.dsim_emu_step_forward(C.byref(desc), C.c_int(N), _p(q), _p(qd), _p(act), _p(m), C.c_float(h), C.c_int(1), C.c_int(1),
+                                   _p(qo), _p(qdo), _p(ck))
+    assert rc == 0, rc
+    gq_out = np.zeros_like(q)
+    gq, gqd, ga, gm = np.zeros_like(q), np.zeros_like(qd), np.zeros_like(act), np.zeros_like(m)
+    rc = lib.dsim_emu_step_backward(C.byref(desc), C.c_int(N), _p(ck), _p(act), _p(m), C.c_float(h), C.c_int(1), C.c_int(1),
+                                    _p(gq_out), _p(gqd_out), _p(gq), _p(gqd), _p(ga), _p(gm))
+    _mode(lib, False, 1)
+    assert rc == 0, rc
+    return gq, ga, (gm if t.n_muscles else None)
+
+
+# ---- the fixtures' inputs and the bounds ---------------------------------------------------------------------------------
+def inputs(g):
+    """(q, qd, act, mact | None, muscles) of a step fixture"""
+    muscles = "muscle_act_in" in g
+    return g["q_in"], g["qd_in"], g["act_in"], (g["muscle_act_in"] if muscles else None), muscles
+
+
+def cotangents(dyn, tag):
+    c = dict(tau=(dyn["c_tau"], None, None), qdd=(None, dyn["c_qdd"], None), fs=(None, None, dyn["c_fs"]),
+             all=(dyn["c_tau"], dyn["c_qdd"], dyn["c_fs"]))
+    return c[tag]
+
+
+def rows_err(got, ref, rows):
+    """max-norm relative error over the given states, on the scale of the reference tensor of the SAME cotangent set (the unit of
+    that set's recorded noise)"""
+    B = ref.shape[0]
+    a, b = np.asarray(got, np.float64).reshape(B, -1), np.asarray(ref, np.float64).reshape(B, -1)
+    if not len(rows):
+        return 0.0
+    return float(np.abs(a[rows] - b[rows]).max() / (np.abs(b).max() + 1e-30))
+
+
+def adjoint_plan(env, dyn, muscles):
+    """per cotangent set and tensor: (states compared, bound, recorded noise over them); and the excluded (state, tensor) pairs
+    with the sets they are excluded in and their largest recorded noise"""
+    plan, excluded = {}, {}
+    for tag in COTANGENTS:
+        for name in ("gq", "gqd", "gmact" if muscles else "gact"):
+            noise = np.asarray(dyn["noise_" + name + ("" if tag == "all" else "_" + tag)], np.float64)
+            rows = np.nonzero(noise <= EXCLUDE)[0]
+            for b in np.nonzero(noise > EXCLUDE)[0]:
+                sets, worst = excluded.get((int(b), name), ((), 0.0))
+                excluded[(int(b), name)] = (sets + (tag,), max(worst, float(noise[b])))
+            worst = float(noise[rows].max()) if len(rows) else 0.0
+            plan[(tag, name)] = (rows, min(max(FACTOR * worst, FLOOR), CEIL), worst)
+    assert len(excluded) <= MAX_EXCLUDED.get(env, 0) and all(n == "gq" for _, n in excluded), (env, excluded)
+    return plan, sorted(excluded.items())
+
+
+def composite_bound(dyn, name, floor):
+    return max(FACTOR * float(np.max(dyn["comp_noise_" + name])), floor)
