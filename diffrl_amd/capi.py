@@ -111,7 +111,7 @@ class DsimError(RuntimeError):
 
 
 _libs = {}
-EXPECTED_ABI = 109   # dsim_version() of the library this binding was written against (argument lists of include/dsim.h)
+EXPECTED_ABI = 110   # dsim_version() of the library this binding was written against (argument lists of include/dsim.h)
 
 
 def lib():
@@ -153,6 +153,9 @@ def load(path):
                                      vp]
     L.dsim_step_backward_literal.argtypes = [vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     L.dsim_step_backward_literal.restype = C.c_int
+    L.dsim_step_backward_multi.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp,
+                                           vp, vp]
+    L.dsim_step_jacobian.argtypes = [vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp]
     L.dsim_literal_scratch_floats.argtypes = [vp]
     L.dsim_literal_scratch_floats.restype = C.c_int64
     ep = C.POINTER(EnvSpec)
@@ -170,7 +173,7 @@ def load(path):
     for fn in (L.dsim_model_create, L.dsim_model_destroy, L.dsim_step_forward, L.dsim_step_backward,
                L.dsim_env_step_forward, L.dsim_env_step_backward, L.dsim_env_observe, L.dsim_model_status,
                L.dsim_body_transforms, L.dsim_body_kinematics, L.dsim_body_kinematics_backward, L.dsim_joint_dynamics,
-               L.dsim_joint_dynamics_backward):
+               L.dsim_joint_dynamics_backward, L.dsim_step_backward_multi, L.dsim_step_jacobian):
         fn.restype = C.c_int
     _libs[path] = L
     return L
@@ -186,4 +189,4 @@ EXPORTS = ("dsim_last_error", "dsim_version", "dsim_model_create", "dsim_model_d
            "dsim_ckpt_floats", "dsim_ckpt_floats_mm", "dsim_model_set_ckpt_mode",
            "dsim_step_forward", "dsim_step_backward", "dsim_step_backward_literal", "dsim_literal_scratch_floats", "dsim_env_step_forward", "dsim_env_step_backward",
            "dsim_env_observe", "dsim_model_status", "dsim_body_transforms", "dsim_body_kinematics", "dsim_body_kinematics_backward",
-           "dsim_joint_dynamics", "dsim_joint_dynamics_backward")
+           "dsim_joint_dynamics", "dsim_joint_dynamics_backward", "dsim_step_backward_multi", "dsim_step_jacobian")

@@ -4288,6 +4288,43 @@ DSIM_FN void dsim_sim_step_backward(const Ctx& c, Exec& ex, int substeps, int mm
     });
 }
 
+// Many cotangents per environment against ONE checkpoint (dsim_step_backward_multi / dsim_step_jacobian): a launch of
+// n_envs * n_cot workgroups, workgroup b = e * n_cot + k runs dsim_sim_step_backward of environment e with cotangent pair k.
+// The checkpoint, act and mact of an environment are read-only and shared by its n_cot sweeps.  Cotangent rows come from one set
+// for all environments (cot_shared) or from the environment's own; every array has an explicit ROW STRIDE in floats, so that
+// the Jacobian call reads its seeds as rows of an identity matrix and writes [gq_in | gqd_in] side by side into a row of J_state.
+struct DsimMultiArgs {
+    int n_cot, cot_shared;
+    long long ckpt_stride;            // floats per environment (dsim_ckpt_words)
+    const float *ckpt, *act, *mact;   // [n_envs][...]; mact null without muscles
+    const float *gq_out, *gqd_out;    // row k (shared) or e * n_cot + k
+    int gq_out_stride, gqd_out_stride;
+    float *gq_in, *gqd_in, *gact, *gmact;   // row e * n_cot + k; gact / gmact may be null
+    int gq_in_stride, gqd_in_stride, gact_stride, gmact_stride;
+};
+struct DsimMultiSlot {
+    int env, cot;
+    const float *ckpt, *act, *mact, *gq_out, *gqd_out;
+    float *gq_in, *gqd_in, *gact, *gmact;
+};
+// (block index -> environment, cotangent, pointers): the one statement of the mapping, run by the kernels and the host harness
+DSIM_FN DsimMultiSlot dsim_multi_slot(const DsimMultiArgs& a, int block, int nd, int M) {
+    DsimMultiSlot s;
+    s.env = block / a.n_cot;
+    s.cot = block - s.env * a.n_cot;
+    const size_t e = (size_t)s.env, row = (size_t)block, crow = a.cot_shared ? (size_t)s.cot : row;
+    s.ckpt = a.ckpt + e * (size_t)a.ckpt_stride;
+    s.act = a.act + e * (size_t)nd;
+    s.mact = (a.mact && M) ? a.mact + e * (size_t)M : nullptr;
+    s.gq_out = a.gq_out + crow * (size_t)a.gq_out_stride;
+    s.gqd_out = a.gqd_out + crow * (size_t)a.gqd_out_stride;
+    s.gq_in = a.gq_in + row * (size_t)a.gq_in_stride;
+    s.gqd_in = a.gqd_in + row * (size_t)a.gqd_in_stride;
+    s.gact = a.gact ? a.gact + row * (size_t)a.gact_stride : nullptr;
+    s.gmact = (a.gmact && M) ? a.gmact + row * (size_t)a.gmact_stride : nullptr;
+    return s;
+}
+
 // ================================================================================================
 // fused environment surface: action clip/scale -> joint_act / muscle
 // activations, observation vector and reward computed by the step kernels, adjoint fused likewise.

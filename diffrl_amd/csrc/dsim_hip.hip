@@ -798,6 +798,20 @@ __global__ __launch_bounds__((DSIM_NL * NW * (MODE == 1 ? 2 : 1)), DSIM_WIDE_WAV
                            lit ? lit + (size_t)e * (nq + nd + nd * nd) : nullptr);
 }
 
+// dsim_step_backward_multi / dsim_step_jacobian: one workgroup per (environment, cotangent) pair -- the grid is n_envs * n_cot --
+// each running the step adjoint above against the environment's checkpoint, which its n_cot sweeps share read-only.  Plain
+// launch mode only (the helper-wave kernels compute the same bits); dsim_core.hpp: dsim_multi_slot maps the block index.
+template <class O, class D, int NW, bool LEAN>
+__global__ __launch_bounds__((DSIM_NL * NW), DSIM_WIDE_WAVES(NW)) void dsim_bwd_multi_kernel(KCommonT<O, D> k, DsimMultiArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    if ((long long)blockIdx.x >= (long long)k.n_envs * a.n_cot) return;
+    DevExec<NW, dsim_pf_regs<O, NW, LEAN, DSIM_MODE_PLAIN>(), dsim_const_words<O>(), false, 1> ex;
+    auto c = start_env<LEAN, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    const DsimMultiSlot s = dsim_multi_slot(a, (int)blockIdx.x, k.d.nd, k.d.M);
+    dsim_sim_step_backward(c, ex, k.substeps, k.mm_freq, s.ckpt, s.act, s.mact, s.gq_out, s.gqd_out, s.gq_in, s.gqd_in, s.gact,
+                           s.gmact);
+}
+
 // dsim_step_backward_literal, second launch: gq_in[quaternion block of joint j] += rho_j q_j (dsim_literal.hpp).  One thread per
 // (environment, link); threads of links without a quaternion joint leave at once.  Run-time layout for every model.
 // row_words: floats of one substep's checkpoint row in the model's checkpoint mode (both modes start a row with q, qd).
@@ -1001,6 +1015,7 @@ int match_variant(const DsimLayout& lay) {
 struct dsim_model {
     DsimLayout lay;
     uint32_t* d_cblob = nullptr;
+    float* d_eye = nullptr;   // (n_q + n_qd)-square identity: the seed rows of dsim_step_jacobian
     int variant = V_GENERIC;
     int waves = 1;   // wavefronts per environment: 1 or DSIM_WAVES_WIDE
     int lean = 0;    // checkpoint mode (dsim_model_set_ckpt_mode)
@@ -1228,7 +1243,7 @@ int make_spec(const dsim_model* m, const dsim_env_spec* e, DsimEnvSpec& sp) {
 extern "C" {
 
 const char* dsim_last_error(void) { return g_err.c_str(); }
-int dsim_version(void) { return 109; }
+int dsim_version(void) { return 110; }
 
 int dsim_model_create(const dsim_model_desc* desc, dsim_model** out) {
     if (!desc || !out) return fail(DSIM_ERR_INVALID, "null argument");
@@ -1261,6 +1276,14 @@ int dsim_model_create(const dsim_model_desc* desc, dsim_model** out) {
     if (e == hipSuccess) e = hipMalloc(&m->d_cblob, sizeof(uint32_t) * m->lay.cblob.size());
     if (e == hipSuccess)
         e = hipMemcpy(m->d_cblob, m->lay.cblob.data(), sizeof(uint32_t) * m->lay.cblob.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const size_t K = (size_t)m->lay.d.nq + (size_t)m->lay.d.nd;
+        std::string eye(K * K * sizeof(float), '\0');
+        float* h_eye = reinterpret_cast<float*>(&eye[0]);
+        for (size_t i = 0; i < K; ++i) h_eye[i * K + i] = 1.0f;
+        e = hipMalloc(&m->d_eye, eye.size());
+        if (e == hipSuccess) e = hipMemcpy(m->d_eye, h_eye, eye.size(), hipMemcpyHostToDevice);
+    }
     if (e == hipSuccess && (2 * bytes > 64 * 1024 || 2 * fbytes > 64 * 1024)) {   // (2 x: pair launches)
         // Opt in to > 64 KiB of dynamic LDS.  The attribute belongs to the kernel FUNCTION, not to this model: two models
         // that share a kernel variant (e.g. two user models on the generic kernels) must not lower each other's limit,
@@ -1290,11 +1313,18 @@ int dsim_model_create(const dsim_model_desc* desc, dsim_model** out) {
             if (e == hipSuccess)
                 e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_joint_dyn_bwd_kernel<O, D, NW>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_bwd_multi_kernel<O, D, NW, false>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess)
+                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_bwd_multi_kernel<O, D, NW, true>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             return 0;
         });
     }
     if (e != hipSuccess) {
         if (m->d_cblob) (void)hipFree(m->d_cblob);
+        if (m->d_eye) (void)hipFree(m->d_eye);
         if (m->h_status) (void)hipHostFree(const_cast<int*>(m->h_status));
         delete m;
         return hip_fail(e, "dsim_model_create");
@@ -1341,6 +1371,7 @@ extern "C" {
 int dsim_model_destroy(dsim_model* m) {
     if (!m) return DSIM_OK;
     if (m->d_cblob) (void)hipFree(m->d_cblob);
+    if (m->d_eye) (void)hipFree(m->d_eye);
     if (m->h_status) (void)hipHostFree(const_cast<int*>(m->h_status));
     delete m;
     return DSIM_OK;
@@ -1400,6 +1431,74 @@ int dsim_step_backward(const dsim_model* m, int n_envs, const float* ckpt, const
                        float* gqd_in, float* gact, float* gmuscle_act, void* hip_stream) {
     return step_backward(m, n_envs, ckpt, act, muscle_act, dt, substeps, mm_freq, gq_out, gqd_out, gq_in, gqd_in, gact, gmuscle_act,
                          nullptr, hip_stream);
+}
+
+// Largest grid of dsim_step_backward_multi / dsim_step_jacobian: n_envs * n_cot workgroups of up to 256 lanes, the launch's
+// thread count below 2^32.
+#define DSIM_MULTI_MAX_BLOCKS ((1ll << 24) - 1)
+
+static int step_backward_multi(const dsim_model* m, int n_envs, float dt, int substeps, int mm_freq, const DsimMultiArgs& a,
+                               void* hip_stream) {
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const unsigned blocks = (unsigned)((long long)n_envs * a.n_cot);
+    return dispatch(m, [&](auto o, auto d, auto nw) {
+        using O = decltype(o);
+        using D = decltype(d);
+        constexpr int NW = decltype(nw)::value;
+        auto k = make_k(m, o, d, n_envs, dt, substeps, mm_freq);
+        DsimMultiArgs args = a;
+        args.ckpt_stride = k.ckpt_stride;
+        const size_t bytes = (size_t)m->lay.o.total_words * 4;
+        if (m->lean) hipLaunchKernelGGL((dsim_bwd_multi_kernel<O, D, NW, true>), dim3(blocks), dim3(DSIM_NL * NW), bytes, st, k, args);
+        else hipLaunchKernelGGL((dsim_bwd_multi_kernel<O, D, NW, false>), dim3(blocks), dim3(DSIM_NL * NW), bytes, st, k, args);
+        return launched("launch dsim_bwd_multi_kernel");
+    });
+}
+
+static int check_multi(const dsim_model* m, int n_envs, int n_cot, const float* ckpt, const float* act, const float* muscle_act,
+                       float dt, int substeps, int mm_freq) {
+    int rc = check_common(m, n_envs, dt, substeps, mm_freq);
+    if (rc) return rc;
+    if (n_cot <= 0) return fail(DSIM_ERR_INVALID, "n_cot must be positive");
+    if (!ckpt || !act) return fail(DSIM_ERR_INVALID, "null pointer (ckpt/act)");
+    if (m->lay.d.M > 0 && !muscle_act) return fail(DSIM_ERR_INVALID, "model has muscles but muscle_act is null");
+    if ((long long)n_envs * n_cot > DSIM_MULTI_MAX_BLOCKS)
+        return fail(DSIM_ERR_LIMIT, "n_envs * n_cot = " + std::to_string((long long)n_envs * n_cot) + " workgroups exceed the grid limit of " +
+                                        std::to_string(DSIM_MULTI_MAX_BLOCKS) + ": split the environments over several calls");
+    return DSIM_OK;
+}
+
+int dsim_step_backward_multi(const dsim_model* m, int n_envs, int n_cot, int cot_shared, const float* ckpt, const float* act,
+                             const float* muscle_act, float dt, int substeps, int mm_freq, const float* gq_out,
+                             const float* gqd_out, float* gq_in, float* gqd_in, float* gact, float* gmuscle_act, void* hip_stream) {
+    if (m && n_envs > 0 && n_cot > 0 && (!gq_out || !gqd_out || !gq_in || !gqd_in))
+        return fail(DSIM_ERR_INVALID, "null pointer (grad)");
+    int rc = check_multi(m, n_envs, n_cot, ckpt, act, muscle_act, dt, substeps, mm_freq);
+    if (rc) return rc;
+    const int nq = m->lay.d.nq, nd = m->lay.d.nd, M = m->lay.d.M;
+    DsimMultiArgs a{};
+    a.n_cot = n_cot; a.cot_shared = cot_shared != 0;
+    a.ckpt = ckpt; a.act = act; a.mact = muscle_act;
+    a.gq_out = gq_out; a.gqd_out = gqd_out; a.gq_out_stride = nq; a.gqd_out_stride = nd;
+    a.gq_in = gq_in; a.gqd_in = gqd_in; a.gact = gact; a.gmact = gmuscle_act;
+    a.gq_in_stride = nq; a.gqd_in_stride = nd; a.gact_stride = nd; a.gmact_stride = M;
+    return step_backward_multi(m, n_envs, dt, substeps, mm_freq, a, hip_stream);
+}
+
+int dsim_step_jacobian(const dsim_model* m, int n_envs, const float* ckpt, const float* act, const float* muscle_act, float dt,
+                       int substeps, int mm_freq, float* J_state, float* J_act, float* J_muscle, void* hip_stream) {
+    if (m && n_envs > 0 && !J_state) return fail(DSIM_ERR_INVALID, "null pointer (J_state)");
+    const int K = m ? m->lay.d.nq + m->lay.d.nd : 1;
+    int rc = check_multi(m, n_envs, K, ckpt, act, muscle_act, dt, substeps, mm_freq);
+    if (rc) return rc;
+    const int nq = m->lay.d.nq, nd = m->lay.d.nd, M = m->lay.d.M;
+    DsimMultiArgs a{};
+    a.n_cot = K; a.cot_shared = 1;
+    a.ckpt = ckpt; a.act = act; a.mact = muscle_act;
+    a.gq_out = m->d_eye; a.gqd_out = m->d_eye + nq; a.gq_out_stride = K; a.gqd_out_stride = K;   // row k of the identity
+    a.gq_in = J_state; a.gqd_in = J_state + nq; a.gact = J_act; a.gmact = J_muscle;              // [gq_in | gqd_in] = row k of J_state
+    a.gq_in_stride = K; a.gqd_in_stride = K; a.gact_stride = nd; a.gmact_stride = M;
+    return step_backward_multi(m, n_envs, dt, substeps, mm_freq, a, hip_stream);
 }
 
 int64_t dsim_literal_scratch_floats(const dsim_model* m) {

@@ -32,3 +32,22 @@ class SemiImplicitIntegrator:
         if config.verify_fp and not (torch.isfinite(out.joint_q).all() and torch.isfinite(out.joint_qd).all()):
             raise FloatingPointError("non-finite state after SemiImplicitIntegrator.forward")
         return out
+
+    def linearize(self, model: Model, state_in: State, dt: float, substeps: int, mass_matrix_freq: int):
+        """The step and its Jacobian around state_in: (state_out, A, B) -- for a muscle model (state_out, A, B, B_muscle) -- with
+        A [n_envs, K, K] = d (q', qd') / d (q, qd), B [n_envs, K, n_qd] = d (q', qd') / d joint_act and B_muscle [n_envs, K, M]
+        = d (q', qd') / d muscle_activation, K = n_q + n_qd, rows (q' | qd'), columns of A (q | qd).  One forward launch that
+        keeps its checkpoint and one Jacobian launch (Engine.step_jacobian); everything returned is detached.  The derivative
+        is the one the adjoint defines (include/dsim.h, dsim_step_jacobian): the quaternion blocks of A's q columns are tangent."""
+        eng = model.engine()
+        mact = model.muscle_activation.detach().contiguous() if model.muscle_count else None
+        act = state_in.joint_act.detach().contiguous()
+        dt, substeps, mm = float(dt), int(substeps), int(mass_matrix_freq)
+        with torch.no_grad():
+            q, qd, ckpt = eng.forward(state_in.joint_q.detach().contiguous(), state_in.joint_qd.detach().contiguous(), act, mact,
+                                      dt, substeps, mm, True, keep_q_in=True)
+            A, B, Bm = eng.step_jacobian(ckpt, act, mact, dt, substeps, mm)
+        out = State(act_like=model.joint_qd, model=model)
+        out.joint_q, out.joint_qd = q.view(state_in.joint_q.shape), qd.view(state_in.joint_qd.shape)
+        out._xf_q = eng.last_q_in
+        return (out, A, B, Bm) if model.muscle_count else (out, A, B)

@@ -301,6 +301,62 @@ class Engine:
                                                         _ptr(gact), _ptr(gm), st))
         return gq, gqd, gact, gm
 
+    def backward_multi(self, ckpt, act, mact, dt, substeps, mm_freq, gq_out, gqd_out, shared=False):
+        """dsim_step_backward_multi: K cotangent pairs per environment against one checkpoint, one launch of n_envs * K
+        workgroups.  gq_out [K, n_q] / gqd_out [K, n_qd] with shared=True (one set for every environment), [n_envs, K, n_q] /
+        [n_envs, K, n_qd] otherwise -> (gq_in [n_envs, K, n_q], gqd_in [n_envs, K, n_qd], gact [n_envs, K, n_qd],
+        gmuscle_act [n_envs, K, M] | None); row (e, k) is what backward() returns for environment e and pair k, bit for bit."""
+        self._check_ckpt(ckpt, substeps, mm_freq)
+        n = ckpt.shape[0]
+        gq_out, gqd_out = gq_out.contiguous(), gqd_out.contiguous()
+        self._check(gq_out, self.n_q, "gq_out")
+        self._check(gqd_out, self.n_qd, "gqd_out")
+        K = gq_out.numel() // (self.n_q * (1 if shared else n))
+        if K <= 0 or gq_out.numel() != (1 if shared else n) * K * self.n_q or gqd_out.numel() != (1 if shared else n) * K * self.n_qd:
+            raise capi.DsimError("gq_out / gqd_out must hold the same number K >= 1 of cotangent rows%s"
+                                 % ("" if shared else " for each of the %d environments" % n))
+        self._check_act(act, mact, n)
+        M = self.n_muscles
+        gq = torch.empty((n, K, self.n_q), dtype=torch.float32, device=self.device)
+        gqd = torch.empty((n, K, self.n_qd), dtype=torch.float32, device=self.device)
+        gact = torch.empty((n, K, self.n_qd), dtype=torch.float32, device=self.device)
+        gm = torch.empty((n, K, M), dtype=torch.float32, device=self.device) if M else None
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self._ck(self._lib.dsim_step_backward_multi(self._h, n, K, 1 if shared else 0, _ptr(ckpt), _ptr(act),
+                                                          _ptr(mact) if M else None, C.c_float(dt), substeps, mm_freq,
+                                                          _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gm), st))
+        return gq, gqd, gact, gm
+
+    def step_jacobian(self, ckpt, act, mact, dt, substeps, mm_freq):
+        """dsim_step_jacobian: the Jacobian of the step that wrote `ckpt`, one launch -> (J_state [n_envs, K, K], J_act
+        [n_envs, K, n_qd], J_muscle [n_envs, K, M] | None) with K = n_q + n_qd: row k is the gradient of output coordinate k
+        of (q_out | qd_out), the columns of J_state are (q_in | qd_in).  The derivative is the adjoint's (include/dsim.h); the
+        quaternion blocks of the q_in columns are tangent."""
+        self._check_ckpt(ckpt, substeps, mm_freq)
+        n = ckpt.shape[0]
+        self._check_act(act, mact, n)
+        K, M = self.n_q + self.n_qd, self.n_muscles
+        J = torch.empty((n, K, K), dtype=torch.float32, device=self.device)
+        Ja = torch.empty((n, K, self.n_qd), dtype=torch.float32, device=self.device)
+        Jm = torch.empty((n, K, M), dtype=torch.float32, device=self.device) if M else None
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self._ck(self._lib.dsim_step_jacobian(self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact) if M else None, C.c_float(dt),
+                                                    substeps, mm_freq, _ptr(J), _ptr(Ja), _ptr(Jm), st))
+        return J, Ja, Jm
+
+    def _check_act(self, act, mact, n):
+        """the actuation a checkpoint of n environments is consumed with"""
+        self._check(act, self.n_qd, "joint_act")
+        if act.numel() != n * self.n_qd:
+            raise capi.DsimError("joint_act does not match the checkpoint's %d environments" % n)
+        if self.n_muscles:
+            if mact is None:
+                raise capi.DsimError("model has muscles but muscle_activation is None")
+            self._check(mact, self.n_muscles, "muscle_activation")
+            if mact.numel() != n * self.n_muscles:
+                raise capi.DsimError("muscle_activation does not match the checkpoint's %d environments" % n)
 
     # ---- fused environment surface ------------------------------------------------------------------
     def env_forward(self, spec, q, qd, actions, dt, substeps, mm_freq, need_ckpt, episode=None):

@@ -191,6 +191,43 @@ int dsim_step_backward_literal(const dsim_model* m, int n_envs,
                                const float* gq_out, const float* gqd_out,
                                float* gq_in, float* gqd_in, float* gact, float* gmuscle_act, float* scratch, void* hip_stream);
 
+/* Step Jacobians (ABI 110): many cotangents per environment from ONE checkpoint, in one launch of n_envs * n_cot workgroups
+ * (workgroup e * n_cot + k: environment e, cotangent k; the plain one-environment-per-workgroup adjoint kernels).
+ *
+ * K cotangent pairs per environment against ONE checkpoint (read-only, shared by the K sweeps of an environment).
+ * cot_shared != 0: gq_out [K][n_q], gqd_out [K][n_qd] are one set used by every environment;
+ * cot_shared == 0: gq_out [N][K][n_q], gqd_out [N][K][n_qd].
+ * Outputs WRITTEN: gq_in [N][K][n_q], gqd_in [N][K][n_qd], gact [N][K][n_qd] or NULL, gmuscle_act [N][K][M] or NULL.
+ *
+ * Both calls follow the conventions of dsim_step_backward above, row by row -- row (e, k) equals, bit for bit, what
+ * dsim_step_backward returns for environment e with cotangent pair k:
+ *   - the derivative is the one the adjoint defines: the factor treated as constant, dH accumulated over a mass-matrix group,
+ *     the min / max / clamp rules of the reference;
+ *   - the quaternion blocks of the q_in columns are TANGENT: they have no component along the quaternion (wrench form; there
+ *     is no literal variant of these calls);
+ *   - the checkpoint is consumed in the mode it was written in (DSIM_CKPT_FULL or DSIM_CKPT_LEAN), with the same act /
+ *     muscle_act, dt, substeps and mm_freq as the forward call;
+ *   - outputs are written, not accumulated; no host synchronisation, no atomics, the caller's stream;
+ *   - n_cot <= 0 or a null required pointer (ckpt, act, muscle_act of a muscle model, gq_out, gqd_out, gq_in, gqd_in, J_state):
+ *     DSIM_ERR_INVALID; n_envs * n_cot beyond the grid limit of 2^24 - 1 workgroups: DSIM_ERR_LIMIT, checked before anything
+ *     is launched. */
+int dsim_step_backward_multi(const dsim_model* m, int n_envs, int n_cot, int cot_shared,
+                             const float* ckpt, const float* act, const float* muscle_act,
+                             float dt, int substeps, int mm_freq,
+                             const float* gq_out, const float* gqd_out,
+                             float* gq_in, float* gqd_in, float* gact, float* gmuscle_act, void* hip_stream);
+/* The whole Jacobian: row k is the gradient of output coordinate k of (q_out | qd_out), K = n_q + n_qd, seeded in the launch
+ * (rows of an identity matrix the model holds on the device: n_cot = K, shared).
+ * J_state [N][K][n_q + n_qd] (columns: q_in | qd_in), J_act [N][K][n_qd] or NULL, J_muscle [N][K][M] or NULL.
+ * Rows and columns of a quaternion block: a COLUMN block (q_in) is tangent, as above -- J_state[e][k][block] . quat_in = 0; a ROW
+ * of a quaternion output coordinate is the gradient of that coordinate of the renormalised quaternion, so the four rows of a
+ * block are linearly dependent (quat_out^T rows = 0 to first order): A = J_state is the derivative in the redundant
+ * coordinates, of rank n_q + n_qd minus the number of quaternion blocks. */
+int dsim_step_jacobian(const dsim_model* m, int n_envs,
+                       const float* ckpt, const float* act, const float* muscle_act,
+                       float dt, int substeps, int mm_freq,
+                       float* J_state, float* J_act, float* J_muscle, void* hip_stream);
+
 /* Derived body transforms of a joint state: X_sc[N][L][7] (link frames in the world, what eval_rigid_fk writes to
  * State.body_X_sc, sim.py:1638-1678) and, if X_sm is not NULL, X_sm[N][L][7] = X_sc o X_cm (State.body_X_sm: the bodies'
  * centre-of-mass frames).  The reference's State carries them after every forward() (model.py:338-392; read by
