@@ -110,6 +110,40 @@ class DsimError(RuntimeError):
     pass
 
 
+# The C ABI of include/dsim.h: name -> (restype, argtypes).  load() applies it and EXPORTS is its key list, so a function is
+# declared here once or not at all (tests/test_capi_cpu.py holds the list against the header).
+_vp, _int, _f = C.c_void_p, C.c_int, C.c_float
+_spec = C.POINTER(EnvSpec)
+_step = [_f, _int, _int]   # dt, substeps, mm_freq
+ABI = {
+    "dsim_last_error": (C.c_char_p, []),
+    "dsim_version": (_int, []),
+    "dsim_model_create": (_int, [C.POINTER(ModelDesc), C.POINTER(_vp)]),
+    "dsim_model_destroy": (_int, [_vp]),
+    "dsim_model_variant": (_int, [_vp]),
+    "dsim_model_device": (_int, [_vp]),
+    "dsim_ckpt_floats": (C.c_int64, [_vp, _int]),
+    "dsim_ckpt_floats_mm": (C.c_int64, [_vp, _int, _int]),
+    "dsim_model_set_ckpt_mode": (_int, [_vp, _int]),
+    "dsim_step_forward": (_int, [_vp, _int] + [_vp] * 4 + _step + [_vp] * 4),
+    "dsim_step_backward": (_int, [_vp, _int] + [_vp] * 3 + _step + [_vp] * 7),
+    "dsim_step_backward_literal": (_int, [_vp, _int] + [_vp] * 3 + _step + [_vp] * 8),
+    "dsim_literal_scratch_floats": (C.c_int64, [_vp]),
+    "dsim_env_step_forward": (_int, [_vp, _spec, _int] + [_vp] * 3 + _step + [_vp] * 5 + [C.POINTER(Episode), _vp]),
+    "dsim_env_step_backward": (_int, [_vp, _spec, _int] + [_vp] * 2 + _step + [_vp] * 9),
+    "dsim_env_observe": (_int, [_vp, _spec, _int] + [_vp] * 6),
+    "dsim_model_status": (_int, [_vp, C.POINTER(_int)]),
+    "dsim_body_transforms": (_int, [_vp, _int] + [_vp] * 4),
+    "dsim_body_kinematics": (_int, [_vp, _int] + [_vp] * 6),
+    "dsim_body_kinematics_backward": (_int, [_vp, _int] + [_vp] * 8),
+    "dsim_joint_dynamics": (_int, [_vp, _int] + [_vp] * 8),
+    "dsim_joint_dynamics_backward": (_int, [_vp, _int] + [_vp] * 12),
+    "dsim_step_backward_multi": (_int, [_vp, _int, _int, _int] + [_vp] * 3 + _step + [_vp] * 7),
+    "dsim_step_jacobian": (_int, [_vp, _int] + [_vp] * 3 + _step + [_vp] * 4),
+}
+EXPORTS = tuple(ABI)
+del _vp, _int, _f, _spec, _step
+
 _libs = {}
 EXPECTED_ABI = 110   # dsim_version() of the library this binding was written against (argument lists of include/dsim.h)
 
@@ -129,52 +163,13 @@ def load(path):
         raise DsimError("HIP extension %s not built: run `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(there is no CPU fallback)" % path)
     L = C.CDLL(path)
-    vp = C.c_void_p
-    L.dsim_last_error.restype = C.c_char_p
-    L.dsim_version.restype = C.c_int
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if int(L.dsim_version()) != EXPECTED_ABI:
         raise DsimError("%s reports ABI version %d, this binding expects %d: stale build or a DSIM_LIB override built "
                         "against other argument lists; rebuild (DSIM_FORCE_REBUILD=1 python __graft_entry__.py)"
                         % (path, int(L.dsim_version()), EXPECTED_ABI))
-    L.dsim_model_create.argtypes = [C.POINTER(ModelDesc), C.POINTER(vp)]
-    L.dsim_model_destroy.argtypes = [vp]
-    L.dsim_model_variant.argtypes = [vp]
-    L.dsim_model_variant.restype = C.c_int
-    L.dsim_model_device.argtypes = [vp]
-    L.dsim_model_device.restype = C.c_int
-    L.dsim_ckpt_floats.argtypes = [vp, C.c_int]
-    L.dsim_ckpt_floats.restype = C.c_int64
-    L.dsim_ckpt_floats_mm.argtypes = [vp, C.c_int, C.c_int]
-    L.dsim_ckpt_floats_mm.restype = C.c_int64
-    L.dsim_model_set_ckpt_mode.argtypes = [vp, C.c_int]
-    L.dsim_model_set_ckpt_mode.restype = C.c_int
-    L.dsim_step_forward.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.dsim_step_backward.argtypes = [vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp,
-                                     vp]
-    L.dsim_step_backward_literal.argtypes = [vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.dsim_step_backward_literal.restype = C.c_int
-    L.dsim_step_backward_multi.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp,
-                                           vp, vp]
-    L.dsim_step_jacobian.argtypes = [vp, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp]
-    L.dsim_literal_scratch_floats.argtypes = [vp]
-    L.dsim_literal_scratch_floats.restype = C.c_int64
-    ep = C.POINTER(EnvSpec)
-    L.dsim_env_step_forward.argtypes = [vp, ep, C.c_int, vp, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp,
-                                        C.POINTER(Episode), vp]
-    L.dsim_env_step_backward.argtypes = [vp, ep, C.c_int, vp, vp, C.c_float, C.c_int, C.c_int, vp, vp, vp, vp, vp,
-                                         vp, vp, vp, vp]
-    L.dsim_env_observe.argtypes = [vp, ep, C.c_int, vp, vp, vp, vp, vp, vp]
-    L.dsim_model_status.argtypes = [vp, C.POINTER(C.c_int)]
-    L.dsim_body_transforms.argtypes = [vp, C.c_int, vp, vp, vp, vp]
-    L.dsim_body_kinematics.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp]
-    L.dsim_body_kinematics_backward.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.dsim_joint_dynamics.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.dsim_joint_dynamics_backward.argtypes = [vp, C.c_int] + [vp] * 12
-    for fn in (L.dsim_model_create, L.dsim_model_destroy, L.dsim_step_forward, L.dsim_step_backward,
-               L.dsim_env_step_forward, L.dsim_env_step_backward, L.dsim_env_observe, L.dsim_model_status,
-               L.dsim_body_transforms, L.dsim_body_kinematics, L.dsim_body_kinematics_backward, L.dsim_joint_dynamics,
-               L.dsim_joint_dynamics_backward, L.dsim_step_backward_multi, L.dsim_step_jacobian):
-        fn.restype = C.c_int
     _libs[path] = L
     return L
 
@@ -184,9 +179,3 @@ def check(rc, L=None):
     if rc != 0:
         raise DsimError("dsim error %d: %s" % (rc, (L or lib()).dsim_last_error().decode()))
 
-
-EXPORTS = ("dsim_last_error", "dsim_version", "dsim_model_create", "dsim_model_destroy", "dsim_model_variant", "dsim_model_device",
-           "dsim_ckpt_floats", "dsim_ckpt_floats_mm", "dsim_model_set_ckpt_mode",
-           "dsim_step_forward", "dsim_step_backward", "dsim_step_backward_literal", "dsim_literal_scratch_floats", "dsim_env_step_forward", "dsim_env_step_backward",
-           "dsim_env_observe", "dsim_model_status", "dsim_body_transforms", "dsim_body_kinematics", "dsim_body_kinematics_backward",
-           "dsim_joint_dynamics", "dsim_joint_dynamics_backward", "dsim_step_backward_multi", "dsim_step_jacobian")

@@ -2621,37 +2621,8 @@ DSIM_FN void dsim_sim_step_forward(const Ctx& c, Exec& ex, int substeps, int mm_
     });
 }
 
-// Derived body transforms of a given joint state (dsim_body_transforms, include/dsim.h): what the reference's State carries as
-// body_X_sc / body_X_sm (model.py:338-392, filled by eval_rigid_fk, sim.py:1638-1678).  The kinematics phase of the step
-// kernels, run once on q with qd = 0, then X_sc [L][7] and X_sm = X_sc o X_cm (joint_X_cm has an identity rotation,
-// model.py:1745-1747: p_sm = p_sc + R_sc com, r_sm = r_sc) go to global memory.
-template <class Ctx, class Exec>
-DSIM_FN void dsim_body_transforms_only(const Ctx& c, Exec& ex, const float* g_q, float* g_xsc, float* g_xsm) {
-    ex.begin_request();
-    ex.begin();
-    dsim_init_static(c, ex);
-    ex.run_both([&](int lane) { dsim_topo_init<false>(c, ex, lane); });
-    ex.run([&](int lane) {
-        for (int k = lane; k < c.d.nq; k += Exec::NL) WF(q)[k] = g_q[k];
-        for (int k = lane; k < c.d.nd; k += Exec::NL) WF(qd)[k] = 0.f;
-    });
-    dsim_fwd_kinematics(c, ex);
-    ex.run([&](int lane) {
-        for (int it = lane; it < 7 * c.d.L; it += Exec::NL) g_xsc[it] = WF(xsc)[it];
-        if (g_xsm) {
-            for (int i = lane; i < c.d.L; i += Exec::NL) {
-                const v3 p = ld3(WF(xsc) + 7 * i);
-                const q4 r = ldq(WF(xsc) + 7 * i + 3);
-                const v3 pm = rotate(r, ld3(CF(com) + 3 * i)) + p;
-                float* o = g_xsm + 7 * i;
-                o[0] = pm.x; o[1] = pm.y; o[2] = pm.z; o[3] = r.x; o[4] = r.y; o[5] = r.z; o[6] = r.w;
-            }
-        }
-    });
-}
-
 // Differentiable kinematic read-out of a given (q, qd) (dsim_body_kinematics / dsim_body_kinematics_backward, include/dsim.h):
-// X_sc, X_sm as above and the world-frame spatial twists v_s [L][6] = (w, v) of every link about the WORLD ORIGIN (the
+// X_sc, X_sm (explained in front of dsim_body_kin_forward below) and the world-frame spatial twists v_s [L][6] = (w, v) of every link about the WORLD ORIGIN (the
 // reference's body_v_s, sim.py:1716-1789: the velocity of a point p of the link is v + w x p) -- the kinematics phase of the
 // step kernels on the caller's q AND qd -- and the reverse pass from cotangents on the three tensors to cotangents on (q, qd).
 // Plain code on the general helpers (dsim_subtree_sum is valid for every kernel variant): one kinematics pass, not a substep loop.
@@ -2665,6 +2636,11 @@ template <class Ctx, class Exec> DSIM_FN void dsim_body_kin_load(const Ctx& c, E
         for (int k = lane; k < c.d.nd; k += Exec::NL) WF(qd)[k] = g_qd ? g_qd[k] : 0.f;   // no qd: poses only
     });
 }
+// Without qd, v_s and status words this is dsim_body_transforms (include/dsim.h), the derived body transforms of a given joint
+// state: what the reference's State carries as body_X_sc / body_X_sm (model.py:338-392, filled by eval_rigid_fk,
+// sim.py:1638-1678).  The kinematics phase of the step kernels, run once on q with qd = 0, then X_sc [L][7] and
+// X_sm = X_sc o X_cm (joint_X_cm has an identity rotation, model.py:1745-1747: p_sm = p_sc + R_sc com, r_sm = r_sc) go to
+// global memory.
 template <class Ctx, class Exec>
 DSIM_FN void dsim_body_kin_forward(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, float* g_xsc, float* g_xsm,
                                    float* g_vs, int* g_status = nullptr, int env = 0) {

@@ -21,12 +21,14 @@
 
 #include <new>
 #include <string>
+#include <tuple>
 
 #define DSIM_FN __device__ __forceinline__
 #ifndef DSIM_OPAQUE
 #define DSIM_OPAQUE(x) asm volatile("" : "+v"(x))
 #endif
 #include "dsim_core.hpp"
+#include "dsim_abi.hpp"
 #define DSIM_LIT_FN __device__ inline
 #include "dsim_literal.hpp"
 #ifdef DSIM_STATIC_LAYOUTS_FILE   // (python -m diffrl_amd.specialise --header-out: a generated header outside the tree)
@@ -899,21 +901,9 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_env_obs_kernel(KCommonT<O, 
                           obs + (size_t)e * sp.n_obs, rew + e);
 }
 
-template <class O, class D, int NW>
-__global__ __launch_bounds__(DSIM_NL * NW) void dsim_body_xf_kernel(KCommonT<O, D> k, const float* __restrict__ q, float* xsc,
-                                                                  float* xsm) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int e = blockIdx.x;
-    if (e >= k.n_envs) return;
-    DevExec<NW, 6, dsim_const_words<O>(), false> ex;
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex);
-    dsim_body_transforms_only(c, ex, q + (size_t)e * k.d.nq, xsc + (size_t)e * 7 * k.d.L, xsm ? xsm + (size_t)e * 7 * k.d.L : nullptr);
-}
-
-
 // Differentiable kinematic read-out (dsim_core.hpp: dsim_body_kin_forward / dsim_body_kin_backward): one environment per
 // workgroup, plain launch mode.  The forward kernel needs the forward image only; the adjoint re-runs the kinematics phase and
-// uses the cotangent arrays of the adjoint image.
+// uses the cotangent arrays of the adjoint image.  dsim_body_transforms is the forward kernel without qd, v_s and status words.
 template <class O, class D, int NW>
 __global__ __launch_bounds__(DSIM_NL * NW) void dsim_body_kin_kernel(KCommonT<O, D> k, const float* __restrict__ q,
                                                                    const float* __restrict__ qd, float* xsc, float* xsm, float* vs) {
@@ -1204,6 +1194,67 @@ int launch_step(const dsim_model* m, int n_envs, float dt, int substeps, int mm_
     });
 }
 
+// The read-out kernels: one environment per workgroup of NW waves, plain launch mode, no step geometry.  A family names the
+// kernel, the LDS image it runs on (FWD: the forward image, otherwise the adjoint image) and whether the launch enforces the
+// unit-quaternion precondition (CHECKS: the kernel gets the model's status words; otherwise none -- a read-back of whatever state
+// the caller holds, or an adjoint whose forward launch checked the state).
+#define DSIM_READOUT_FAMILY(NAME, IS_FWD, DOES_CHECK)                                                  \
+    struct NAME##_family {                                                                             \
+        static constexpr bool FWD = IS_FWD, CHECKS = DOES_CHECK;                                       \
+        static constexpr const char* what = "launch " #NAME;                                           \
+        template <class O, class D, int NW> static constexpr auto kernel() { return &NAME<O, D, NW>; } \
+    };
+DSIM_READOUT_FAMILY(dsim_env_obs_kernel, true, true)
+DSIM_READOUT_FAMILY(dsim_body_kin_kernel, true, true)
+DSIM_READOUT_FAMILY(dsim_body_kin_bwd_kernel, false, false)
+DSIM_READOUT_FAMILY(dsim_joint_dyn_kernel, true, true)
+DSIM_READOUT_FAMILY(dsim_joint_dyn_bwd_kernel, false, false)
+#undef DSIM_READOUT_FAMILY
+// dsim_body_transforms: the kinematic read-out without qd and v_s, and without the precondition
+struct dsim_body_xf_family : dsim_body_kin_kernel_family {
+    static constexpr bool CHECKS = false;
+};
+// The list of the read-out families: the table below walks it, and launch_readout refuses to compile for a family that is not
+// on it (or derived from one that is), so a kernel cannot be launched without being opted in to its LDS size.
+using dsim_readout_families = std::tuple<dsim_env_obs_kernel_family, dsim_body_kin_kernel_family, dsim_body_kin_bwd_kernel_family,
+                                         dsim_joint_dyn_kernel_family, dsim_joint_dyn_bwd_kernel_family>;
+template <class Fam, class... Listed> constexpr bool dsim_readout_listed(std::tuple<Listed...>*) {
+    return (std::is_base_of<Listed, Fam>::value || ...);
+}
+
+// f(kernel) for every kernel of a model outside the step families: the read-outs above and the multi-cotangent sweep (full and
+// lean checkpoints; step_backward_multi launches it).
+template <class O, class D, int NW, class F, class... Listed> void for_each_readout_kernel(F&& f, std::tuple<Listed...>*) {
+    (f(reinterpret_cast<const void*>(Listed::template kernel<O, D, NW>())), ...);
+    f(reinterpret_cast<const void*>(&dsim_bwd_multi_kernel<O, D, NW, false>));
+    f(reinterpret_cast<const void*>(&dsim_bwd_multi_kernel<O, D, NW, true>));
+}
+template <class O, class D, int NW, class F> void for_each_readout_kernel(F&& f) {
+    for_each_readout_kernel<O, D, NW>(f, static_cast<dsim_readout_families*>(nullptr));
+}
+
+// The one launch site of the read-out kernels.  `args`: the kernel's arguments behind its KCommonT.
+template <class Fam, class... Args> int launch_readout(const dsim_model* m, int n_envs, void* hip_stream, Args... args) {
+    static_assert(dsim_readout_listed<Fam>(static_cast<dsim_readout_families*>(nullptr)), "add the family to dsim_readout_families");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return dispatch(m, [&](auto o, auto d, auto nw) {
+        constexpr int NW = decltype(nw)::value;
+        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
+        if (!Fam::CHECKS) k.status = nullptr;
+        hipLaunchKernelGGL((Fam::template kernel<decltype(o), decltype(d), NW>()), dim3(n_envs), dim3(DSIM_NL * NW),
+                           (size_t)(Fam::FWD ? m->lay.o.fwd_words : m->lay.o.total_words) * 4, st, k, args...);
+        return launched(Fam::what);
+    });
+}
+
+// the model's device / host allocations and the model itself (a model whose creation failed half-way included)
+void free_model(dsim_model* m) {
+    if (m->d_cblob) (void)hipFree(m->d_cblob);
+    if (m->d_eye) (void)hipFree(m->d_eye);
+    if (m->h_status) (void)hipHostFree(const_cast<int*>(m->h_status));
+    delete m;
+}
+
 int make_spec(const dsim_model* m, const dsim_env_spec* e, DsimEnvSpec& sp) {
     if (!e) return fail(DSIM_ERR_INVALID, "null env spec");
     const DsimDims& d = m->lay.d;
@@ -1229,12 +1280,7 @@ int make_spec(const dsim_model* m, const dsim_env_spec* e, DsimEnvSpec& sp) {
         expect = 5;
     }
     if (e->n_obs != expect) return fail(DSIM_ERR_INVALID, "n_obs does not match the observation layout");
-    sp.kind = e->kind; sp.rew_kind = e->rew_kind; sp.n_act = e->n_act; sp.n_obs = e->n_obs;
-    sp.act_offset = e->act_offset; sp.act_muscle = e->act_muscle; sp.obs_actions = e->obs_actions; sp.sanitize = e->sanitize_grads;
-    for (int k = 0; k < 4; ++k) { sp.isr[k] = e->inv_start_rot[k]; sp.pen[k] = e->cartpole_penalties[k]; }
-    sp.tgt_x = e->target_x; sp.tgt_z = e->target_z; sp.term_h = e->termination_height;
-    sp.term_tol = e->termination_tolerance; sp.h_scale = e->height_rew_scale; sp.act_pen = e->action_penalty;
-    sp.vel_scale = e->joint_vel_obs_scaling; sp.act_scale = e->act_scale;
+    sp = dsim_env_spec_copy(*e);
     return DSIM_OK;
 }
 
@@ -1292,41 +1338,16 @@ int dsim_model_create(const dsim_model_desc* desc, dsim_model** out) {
             using O = decltype(o);
             using D = decltype(d);
             constexpr int NW = decltype(nw)::value;
-            for_each_step_kernel<O, D, NW>([&](const void* fn, bool, bool, int) {
+            auto opt_in = [&](const void* fn) {
                 if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            });
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_env_obs_kernel<O, D, NW>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_body_xf_kernel<O, D, NW>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_body_kin_kernel<O, D, NW>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_body_kin_bwd_kernel<O, D, NW>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_joint_dyn_kernel<O, D, NW>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_joint_dyn_bwd_kernel<O, D, NW>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_bwd_multi_kernel<O, D, NW, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(dsim_bwd_multi_kernel<O, D, NW, true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            };
+            for_each_step_kernel<O, D, NW>([&](const void* fn, bool, bool, int) { opt_in(fn); });
+            for_each_readout_kernel<O, D, NW>(opt_in);
             return 0;
         });
     }
     if (e != hipSuccess) {
-        if (m->d_cblob) (void)hipFree(m->d_cblob);
-        if (m->d_eye) (void)hipFree(m->d_eye);
-        if (m->h_status) (void)hipHostFree(const_cast<int*>(m->h_status));
-        delete m;
+        free_model(m);
         return hip_fail(e, "dsim_model_create");
     }
     dsim_helper_capacity(m);
@@ -1370,10 +1391,7 @@ extern "C" {
 
 int dsim_model_destroy(dsim_model* m) {
     if (!m) return DSIM_OK;
-    if (m->d_cblob) (void)hipFree(m->d_cblob);
-    if (m->d_eye) (void)hipFree(m->d_eye);
-    if (m->h_status) (void)hipHostFree(const_cast<int*>(m->h_status));
-    delete m;
+    free_model(m);
     return DSIM_OK;
 }
 
@@ -1542,20 +1560,7 @@ int dsim_env_step_forward(const dsim_model* m, const dsim_env_spec* env, int n_e
             return fail(DSIM_ERR_INVALID, "episode: null pointer (progress/done/reset_q/reset_qd/reset_count)");
         if (episode->reset_pool <= 0) return fail(DSIM_ERR_INVALID, "episode: reset_pool must be positive");
         if (episode->episode_length <= 0) return fail(DSIM_ERR_INVALID, "episode: episode_length must be positive");
-        ep.progress = reinterpret_cast<long long*>(episode->progress);
-        ep.done = reinterpret_cast<long long*>(episode->done);
-        ep.obs_before = episode->obs_before_reset;
-        ep.reset_q = episode->reset_q;
-        ep.reset_qd = episode->reset_qd;
-        ep.reset_count = episode->reset_count;
-        ep.pool = episode->reset_pool;
-        ep.episode_length = episode->episode_length;
-        ep.height_terminate = episode->height_terminate;
-        ep.check_invalid = episode->check_invalid;
-        ep.noise_q = episode->noise_q;
-        ep.noise_qd = episode->noise_qd;
-        ep.noise_angle = episode->noise_angle;
-        ep.seed = episode->seed;
+        ep = dsim_episode_copy(*episode);
     }
     return launch_step<dsim_env_fwd_kernel_family>(m, n_envs, dt, substeps, mm_freq, hip_stream, sp, ep, q_in, qd_in, actions, q_out,
                                                    qd_out, obs, rew, ckpt);
@@ -1583,29 +1588,14 @@ int dsim_env_observe(const dsim_model* m, const dsim_env_spec* env, int n_envs, 
     rc = make_spec(m, env, sp);
     if (rc) return rc;
     if (!q || !qd || !stored_actions || !obs || !rew) return fail(DSIM_ERR_INVALID, "null pointer");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
-        hipLaunchKernelGGL((dsim_env_obs_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
-                           (size_t)m->lay.o.fwd_words * 4, st, k, sp, q, qd, stored_actions, obs, rew);
-        return launched("launch dsim_env_obs_kernel");
-    });
+    return launch_readout<dsim_env_obs_kernel_family>(m, n_envs, hip_stream, sp, q, qd, stored_actions, obs, rew);
 }
 
 int dsim_body_transforms(const dsim_model* m, int n_envs, const float* q, float* X_sc, float* X_sm, void* hip_stream) {
     int rc = check_common(m, n_envs, 1.0f, 1, 1);
     if (rc) return rc;
     if (!q || !X_sc) return fail(DSIM_ERR_INVALID, "null pointer");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
-        k.status = nullptr;   // a read-back of whatever state the caller holds: no precondition to enforce here
-        hipLaunchKernelGGL((dsim_body_xf_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
-                           (size_t)m->lay.o.fwd_words * 4, st, k, q, X_sc, X_sm);
-        return launched("launch dsim_body_xf_kernel");
-    });
+    return launch_readout<dsim_body_xf_family>(m, n_envs, hip_stream, q, (const float*)nullptr, X_sc, X_sm, (float*)nullptr);
 }
 
 int dsim_body_kinematics(const dsim_model* m, int n_envs, const float* q, const float* qd, float* X_sc, float* X_sm, float* v_s,
@@ -1614,14 +1604,7 @@ int dsim_body_kinematics(const dsim_model* m, int n_envs, const float* q, const 
     if (rc) return rc;
     if (!q || !X_sc) return fail(DSIM_ERR_INVALID, "null pointer");
     if ((qd == nullptr) != (v_s == nullptr)) return fail(DSIM_ERR_INVALID, "v_s is returned if and only if qd is given");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
-        hipLaunchKernelGGL((dsim_body_kin_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
-                           (size_t)m->lay.o.fwd_words * 4, st, k, q, qd, X_sc, X_sm, v_s);
-        return launched("launch dsim_body_kin_kernel");
-    });
+    return launch_readout<dsim_body_kin_kernel_family>(m, n_envs, hip_stream, q, qd, X_sc, X_sm, v_s);
 }
 
 int dsim_body_kinematics_backward(const dsim_model* m, int n_envs, const float* q, const float* qd, const float* gX_sc,
@@ -1631,15 +1614,7 @@ int dsim_body_kinematics_backward(const dsim_model* m, int n_envs, const float* 
     if (!q || !gq) return fail(DSIM_ERR_INVALID, "null pointer");
     if ((qd == nullptr) != (gqd == nullptr)) return fail(DSIM_ERR_INVALID, "gqd is returned if and only if qd is given");
     if (!qd && gv_s) return fail(DSIM_ERR_INVALID, "gv_s without qd: there is no v_s output to have a cotangent");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
-        k.status = nullptr;   // the forward launch checked the state
-        hipLaunchKernelGGL((dsim_body_kin_bwd_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
-                           (size_t)m->lay.o.total_words * 4, st, k, q, qd, gX_sc, gX_sm, gv_s, gq, gqd);
-        return launched("launch dsim_body_kin_bwd_kernel");
-    });
+    return launch_readout<dsim_body_kin_bwd_kernel_family>(m, n_envs, hip_stream, q, qd, gX_sc, gX_sm, gv_s, gq, gqd);
 }
 
 int dsim_joint_dynamics(const dsim_model* m, int n_envs, const float* q, const float* qd, const float* act, const float* muscle_act,
@@ -1648,14 +1623,7 @@ int dsim_joint_dynamics(const dsim_model* m, int n_envs, const float* q, const f
     if (rc) return rc;
     if (!q || !qd) return fail(DSIM_ERR_INVALID, "null pointer");
     if (!tau && !qdd && !f_s) return fail(DSIM_ERR_INVALID, "no output: tau, qdd and f_s are all null");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
-        hipLaunchKernelGGL((dsim_joint_dyn_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
-                           (size_t)m->lay.o.fwd_words * 4, st, k, q, qd, act, muscle_act, tau, qdd, f_s);
-        return launched("launch dsim_joint_dyn_kernel");
-    });
+    return launch_readout<dsim_joint_dyn_kernel_family>(m, n_envs, hip_stream, q, qd, act, muscle_act, tau, qdd, f_s);
 }
 
 int dsim_joint_dynamics_backward(const dsim_model* m, int n_envs, const float* q, const float* qd, const float* act,
@@ -1664,15 +1632,8 @@ int dsim_joint_dynamics_backward(const dsim_model* m, int n_envs, const float* q
     int rc = check_common(m, n_envs, 1.0f, 1, 1);
     if (rc) return rc;
     if (!q || !qd || !gq || !gqd) return fail(DSIM_ERR_INVALID, "null pointer");
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    return dispatch(m, [&](auto o, auto d, auto nw) {
-        constexpr int NW = decltype(nw)::value;
-        auto k = make_k(m, o, d, n_envs, 1.0f, 1, 1);
-        k.status = nullptr;   // the forward launch checked the state
-        hipLaunchKernelGGL((dsim_joint_dyn_bwd_kernel<decltype(o), decltype(d), NW>), dim3(n_envs), dim3(DSIM_NL * NW),
-                           (size_t)m->lay.o.total_words * 4, st, k, q, qd, act, muscle_act, gtau, gqdd, gf_s, gq, gqd, gact, gmuscle_act);
-        return launched("launch dsim_joint_dyn_bwd_kernel");
-    });
+    return launch_readout<dsim_joint_dyn_bwd_kernel_family>(m, n_envs, hip_stream, q, qd, act, muscle_act, gtau, gqdd, gf_s, gq, gqd,
+                                                            gact, gmuscle_act);
 }
 
 /* 0 = generic kernels, >0 = index of the specialised variant in use (diagnostics / tests) */

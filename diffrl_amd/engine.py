@@ -91,6 +91,16 @@ class Engine:
     def _ck(self, rc):
         capi.check(rc, self._lib)
 
+    def _call(self, fn, *args):
+        """a launching call of the library on this model: its device current, the current stream as the last argument"""
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self._ck(fn(*args, st))
+
+    def _new(self, *shape):
+        """uninitialised float32 on the model's device"""
+        return torch.empty(shape, dtype=torch.float32, device=self.device)
+
     def _create(self):
         h = C.c_void_p()
         with torch.cuda.device(self.device):
@@ -118,11 +128,9 @@ class Engine:
         self._check(q, self.n_q, "joint_q")
         n = q.numel() // self.n_q
         L = self.template.n_links
-        xsc = torch.empty((n * L, 7), dtype=torch.float32, device=self.device)
-        xsm = torch.empty((n * L, 7), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_body_transforms(self._h, n, _ptr(q), _ptr(xsc), _ptr(xsm), st))
+        xsc = self._new(n * L, 7)
+        xsm = self._new(n * L, 7)
+        self._call(self._lib.dsim_body_transforms, self._h, n, _ptr(q), _ptr(xsc), _ptr(xsm))
         return xsc, xsm
 
     def body_kinematics(self, q, qd=None):
@@ -143,12 +151,10 @@ class Engine:
             if qd.numel() != n * self.n_qd:
                 raise capi.DsimError("state tensors disagree on the number of environments")
         L = self.template.n_links
-        xsc = torch.empty((n * L, 7), dtype=torch.float32, device=self.device)
-        xsm = torch.empty((n * L, 7), dtype=torch.float32, device=self.device)
-        vs = torch.empty((n * L, 6), dtype=torch.float32, device=self.device) if qd is not None else None
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_body_kinematics(self._h, n, _ptr(q), _ptr(qd), _ptr(xsc), _ptr(xsm), _ptr(vs), st))
+        xsc = self._new(n * L, 7)
+        xsm = self._new(n * L, 7)
+        vs = self._new(n * L, 6) if qd is not None else None
+        self._call(self._lib.dsim_body_kinematics, self._h, n, _ptr(q), _ptr(qd), _ptr(xsc), _ptr(xsm), _ptr(vs))
         return xsc, xsm, vs
 
     def body_kinematics_backward(self, q, qd, gxsc, gxsm, gvs):
@@ -160,12 +166,10 @@ class Engine:
                 self._check(g, cols, name)
                 if g.numel() != n * L * cols:
                     raise capi.DsimError("%s has the wrong size" % name)
-        gq = torch.empty(n * self.n_q, dtype=torch.float32, device=self.device)
-        gqd = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device) if qd is not None else None
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_body_kinematics_backward(self._h, n, _ptr(q), _ptr(qd), _ptr(gxsc), _ptr(gxsm), _ptr(gvs),
-                                                               _ptr(gq), _ptr(gqd), st))
+        gq = self._new(n * self.n_q)
+        gqd = self._new(n * self.n_qd) if qd is not None else None
+        self._call(self._lib.dsim_body_kinematics_backward, self._h, n, _ptr(q), _ptr(qd), _ptr(gxsc), _ptr(gxsm), _ptr(gvs),
+                   _ptr(gq), _ptr(gqd))
         return gq, gqd
 
     def joint_dynamics(self, q, qd, act=None, muscle_act=None):
@@ -180,13 +184,11 @@ class Engine:
         """dsim_joint_dynamics on detached contiguous tensors"""
         n = self._dyn_check(q, qd, act, muscle_act)
         L = self.template.n_links
-        tau = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
-        qdd = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
-        fs = torch.empty((n * L, 6), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_joint_dynamics(self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(muscle_act), _ptr(tau), _ptr(qdd),
-                                                   _ptr(fs), st))
+        tau = self._new(n * self.n_qd)
+        qdd = self._new(n * self.n_qd)
+        fs = self._new(n * L, 6)
+        self._call(self._lib.dsim_joint_dynamics, self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(muscle_act), _ptr(tau),
+                   _ptr(qdd), _ptr(fs))
         return tau, qdd, fs
 
     def joint_dynamics_backward(self, q, qd, act, muscle_act, gtau, gqdd, gfs):
@@ -198,14 +200,12 @@ class Engine:
                 self._check(g, 1, name)
                 if g.numel() != size:
                     raise capi.DsimError("%s has the wrong size" % name)
-        gq = torch.empty(n * self.n_q, dtype=torch.float32, device=self.device)
-        gqd = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
-        gact = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
-        gmact = torch.empty(n * M, dtype=torch.float32, device=self.device) if M > 0 else None
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_joint_dynamics_backward(self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(muscle_act), _ptr(gtau),
-                                                            _ptr(gqdd), _ptr(gfs), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gmact), st))
+        gq = self._new(n * self.n_q)
+        gqd = self._new(n * self.n_qd)
+        gact = self._new(n * self.n_qd)
+        gmact = self._new(n * M) if M > 0 else None
+        self._call(self._lib.dsim_joint_dynamics_backward, self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(muscle_act), _ptr(gtau),
+                   _ptr(gqdd), _ptr(gfs), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gmact))
         return gq, gqd, gact, gmact
 
     def _dyn_check(self, q, qd, act, muscle_act):
@@ -230,7 +230,7 @@ class Engine:
     def _alloc_ckpt(self, n, substeps, mm_freq):
         """[n][dsim_ckpt_floats_mm]: per substep the saved forward block (starts with q, qd), then the H^-1 per group"""
         words = int(self._lib.dsim_ckpt_floats_mm(self._h, substeps, mm_freq))
-        return torch.empty((n, words), dtype=torch.float32, device=self.device)
+        return self._new(n, words)
 
     def _check(self, t, cols, name):
         if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
@@ -257,11 +257,8 @@ class Engine:
         if need_ckpt:
             ckpt = self._alloc_ckpt(n, substeps, mm_freq)
         self.last_q_in = None
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_step_forward(self._h, n, _ptr(q), _ptr(qd), _ptr(act),
-                                                   _ptr(mact) if self.n_muscles else None, C.c_float(dt), substeps,
-                                                   mm_freq, _ptr(q_out), _ptr(qd_out), _ptr(ckpt), st))
+        self._call(self._lib.dsim_step_forward, self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(mact) if self.n_muscles else None,
+                   C.c_float(dt), substeps, mm_freq, _ptr(q_out), _ptr(qd_out), _ptr(ckpt))
         if ckpt is not None and keep_q_in:
             self.last_q_in = self.last_substep_q(ckpt, substeps)
         return q_out, qd_out, ckpt
@@ -282,23 +279,18 @@ class Engine:
         n = ckpt.shape[0]
         gq_out = gq_out.contiguous()
         gqd_out = gqd_out.contiguous()
-        gq = torch.empty(n * self.n_q, dtype=torch.float32, device=self.device)
-        gqd = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
-        gact = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
-        gm = torch.empty(n * self.n_muscles, dtype=torch.float32, device=self.device) if self.n_muscles else None
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            if literal:
-                scratch = torch.empty((n, int(self._lib.dsim_literal_scratch_floats(self._h))), dtype=torch.float32, device=self.device)
-                self._ck(self._lib.dsim_step_backward_literal(self._h, n, _ptr(ckpt), _ptr(act),
-                                                                _ptr(mact) if self.n_muscles else None, C.c_float(dt), substeps,
-                                                                mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd),
-                                                                _ptr(gact), _ptr(gm), _ptr(scratch), st))
-            else:
-                self._ck(self._lib.dsim_step_backward(self._h, n, _ptr(ckpt), _ptr(act),
-                                                        _ptr(mact) if self.n_muscles else None, C.c_float(dt), substeps,
-                                                        mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd),
-                                                        _ptr(gact), _ptr(gm), st))
+        gq = self._new(n * self.n_q)
+        gqd = self._new(n * self.n_qd)
+        gact = self._new(n * self.n_qd)
+        gm = self._new(n * self.n_muscles) if self.n_muscles else None
+        if literal:
+            scratch = self._new(n, int(self._lib.dsim_literal_scratch_floats(self._h)))
+            self._call(self._lib.dsim_step_backward_literal, self._h, n, _ptr(ckpt), _ptr(act),
+                       _ptr(mact) if self.n_muscles else None, C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out),
+                       _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gm), _ptr(scratch))
+        else:
+            self._call(self._lib.dsim_step_backward, self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact) if self.n_muscles else None,
+                       C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gm))
         return gq, gqd, gact, gm
 
     def backward_multi(self, ckpt, act, mact, dt, substeps, mm_freq, gq_out, gqd_out, shared=False):
@@ -317,15 +309,13 @@ class Engine:
                                  % ("" if shared else " for each of the %d environments" % n))
         self._check_act(act, mact, n)
         M = self.n_muscles
-        gq = torch.empty((n, K, self.n_q), dtype=torch.float32, device=self.device)
-        gqd = torch.empty((n, K, self.n_qd), dtype=torch.float32, device=self.device)
-        gact = torch.empty((n, K, self.n_qd), dtype=torch.float32, device=self.device)
-        gm = torch.empty((n, K, M), dtype=torch.float32, device=self.device) if M else None
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_step_backward_multi(self._h, n, K, 1 if shared else 0, _ptr(ckpt), _ptr(act),
-                                                          _ptr(mact) if M else None, C.c_float(dt), substeps, mm_freq,
-                                                          _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gm), st))
+        gq = self._new(n, K, self.n_q)
+        gqd = self._new(n, K, self.n_qd)
+        gact = self._new(n, K, self.n_qd)
+        gm = self._new(n, K, M) if M else None
+        self._call(self._lib.dsim_step_backward_multi, self._h, n, K, 1 if shared else 0, _ptr(ckpt), _ptr(act),
+                   _ptr(mact) if M else None, C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd),
+                   _ptr(gact), _ptr(gm))
         return gq, gqd, gact, gm
 
     def step_jacobian(self, ckpt, act, mact, dt, substeps, mm_freq):
@@ -337,13 +327,11 @@ class Engine:
         n = ckpt.shape[0]
         self._check_act(act, mact, n)
         K, M = self.n_q + self.n_qd, self.n_muscles
-        J = torch.empty((n, K, K), dtype=torch.float32, device=self.device)
-        Ja = torch.empty((n, K, self.n_qd), dtype=torch.float32, device=self.device)
-        Jm = torch.empty((n, K, M), dtype=torch.float32, device=self.device) if M else None
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_step_jacobian(self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact) if M else None, C.c_float(dt),
-                                                    substeps, mm_freq, _ptr(J), _ptr(Ja), _ptr(Jm), st))
+        J = self._new(n, K, K)
+        Ja = self._new(n, K, self.n_qd)
+        Jm = self._new(n, K, M) if M else None
+        self._call(self._lib.dsim_step_jacobian, self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact) if M else None, C.c_float(dt),
+                   substeps, mm_freq, _ptr(J), _ptr(Ja), _ptr(Jm))
         return J, Ja, Jm
 
     def _check_act(self, act, mact, n):
@@ -368,43 +356,35 @@ class Engine:
         if qd.numel() != n * self.n_qd or actions.numel() != n * spec.n_act:
             raise capi.DsimError("state / action tensors disagree on the number of environments")
         q_out, qd_out = torch.empty_like(q), torch.empty_like(qd)
-        obs = torch.empty((n, spec.n_obs), dtype=torch.float32, device=self.device)
-        rew = torch.empty(n, dtype=torch.float32, device=self.device)
+        obs = self._new(n, spec.n_obs)
+        rew = self._new(n)
         ckpt = self._alloc_ckpt(n, substeps, mm_freq) if need_ckpt else None
         ep, extra = None, ()
         if episode is not None:
             ep, extra = episode.bind(self, n, spec.n_obs)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_env_step_forward(self._h, C.byref(spec), n, _ptr(q), _ptr(qd), _ptr(actions),
-                                                       C.c_float(dt), substeps, mm_freq, _ptr(q_out), _ptr(qd_out),
-                                                       _ptr(obs), _ptr(rew), _ptr(ckpt),
-                                                       C.byref(ep) if ep is not None else None, st))
+        self._call(self._lib.dsim_env_step_forward, self._h, C.byref(spec), n, _ptr(q), _ptr(qd), _ptr(actions), C.c_float(dt),
+                   substeps, mm_freq, _ptr(q_out), _ptr(qd_out), _ptr(obs), _ptr(rew), _ptr(ckpt),
+                   C.byref(ep) if ep is not None else None)
         return (q_out, qd_out, obs, rew, ckpt) + extra
 
     def env_backward(self, spec, ckpt, actions, dt, substeps, mm_freq, gq_out, gqd_out, gobs, grew, gobs_before=None):
         """any cotangent may be None (= zeros: no fill kernels are launched for unused outputs)"""
         self._check_ckpt(ckpt, substeps, mm_freq)
         n = ckpt.shape[0]
-        gq = torch.empty(n * self.n_q, dtype=torch.float32, device=self.device)
-        gqd = torch.empty(n * self.n_qd, dtype=torch.float32, device=self.device)
-        ga = torch.empty((n, spec.n_act), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_env_step_backward(self._h, C.byref(spec), n, _ptr(ckpt), _ptr(actions),
-                                                        C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out),
-                                                        _ptr(gobs), _ptr(grew), _ptr(gobs_before), _ptr(gq), _ptr(gqd),
-                                                        _ptr(ga), st))
+        gq = self._new(n * self.n_q)
+        gqd = self._new(n * self.n_qd)
+        ga = self._new(n, spec.n_act)
+        self._call(self._lib.dsim_env_step_backward, self._h, C.byref(spec), n, _ptr(ckpt), _ptr(actions), C.c_float(dt),
+                   substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gobs), _ptr(grew), _ptr(gobs_before), _ptr(gq), _ptr(gqd),
+                   _ptr(ga))
         return gq, gqd, ga
 
     def env_observe(self, spec, q, qd, stored_actions):
         n = q.numel() // self.n_q
-        obs = torch.empty((n, spec.n_obs), dtype=torch.float32, device=self.device)
-        rew = torch.empty(n, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            self._ck(self._lib.dsim_env_observe(self._h, C.byref(spec), n, _ptr(q), _ptr(qd), _ptr(stored_actions),
-                                                  _ptr(obs), _ptr(rew), st))
+        obs = self._new(n, spec.n_obs)
+        rew = self._new(n)
+        self._call(self._lib.dsim_env_observe, self._h, C.byref(spec), n, _ptr(q), _ptr(qd), _ptr(stored_actions), _ptr(obs),
+                   _ptr(rew))
         return obs, rew
 
 
@@ -430,7 +410,7 @@ class EpisodeIO:
             if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != k * n * cols:
                 raise capi.DsimError("episode.%s must be a contiguous float32 [pool][n_envs][%d] tensor on %s" % (name, cols, dev))
         done = torch.empty(n, dtype=torch.int64, device=dev)
-        obs_before = torch.empty((n, n_obs), dtype=torch.float32, device=dev) if self.want_obs_before else None
+        obs_before = engine._new(n, n_obs) if self.want_obs_before else None
         ep = capi.Episode()
         ep.progress, ep.done = self.progress.data_ptr(), done.data_ptr()
         ep.obs_before_reset = obs_before.data_ptr() if obs_before is not None else None

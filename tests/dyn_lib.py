@@ -1,7 +1,7 @@
 """Test infrastructure of the differentiable joint dynamics (dsim_joint_dynamics / dsim_joint_dynamics_backward):
 
-* the lane-serial host build of the new phase code (tests/emu/dsim_emu_dyn.cpp), compiled here with the flags of
-  tests/emu/Makefile, for the shipped layouts and for the two user models of tests/golden/user_*.npz;
+* the entry points of the lane-serial host harness for this phase code (tests/emu/dsim_emu_dyn.cpp; tests/emu_lib.py loads the
+  harness), for the shipped layouts and for the two user models of tests/golden/user_*.npz;
 * the bounds of the adjoint comparison against tests/golden/<env>_dyn.npz (tools/gen_dynamics_golden.py), shared by the host
   and the GPU tier.
 
@@ -20,18 +20,13 @@ finite); over all sets at most three (state, tensor) pairs may be excluded, all 
 alone they are quiet and compared).
 """
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from diffrl_amd.capi import make_desc
-from kin_lib import CXXFLAGS, ENVS, USER_MODELS, waves_of  # noqa: F401
+from emu_lib import f32, ptr, emu, emu_user, mode
+from kin_lib import ENVS, USER_MODELS, waves_of  # noqa: F401
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "diffrl_amd", "csrc")
 FACTOR, FLOOR, CEIL, EXCLUDE = 10.0, 1e-5, 1e-3, 3e-4
 MAX_EXCLUDED = {"snu": 3}          # pairs (state, gq); every other model: none
 FWD_BOUND = 1e-4                   # forces and accelerations of one substep (tests/ckpt_fields.py BOUNDS)
@@ -44,80 +39,35 @@ COTANGENTS = ("tau", "qdd", "fs", "all")
 CHECK_MEASURED = 1.48e-5
 CHECK_BOUND = max(10 * CHECK_MEASURED, 1e-5)
 CHECK_H = 1.0 / 960.0
-_libs = {}
-
-
-def _sources():
-    return [os.path.join(EMU_DIR, f) for f in ("dsim_emu_dyn.cpp", "dsim_emu.cpp")] + \
-           [os.path.join(CSRC, f) for f in ("dsim_core.hpp", "dsim_math.hpp", "dsim_layout.hpp", "dsim_static_layouts.hpp",
-                                            "dsim_literal.hpp")] + [os.path.join(ROOT, "include", "dsim.h")]
-
-
-def dyn_emu(user=False):
-    """the host harness with the dynamics entry points: shipped layouts, or (user) those of the two user models"""
-    if user in _libs:
-        return _libs[user]
-    so = os.path.join(EMU_DIR, "libdsim_emu_dyn_user.so" if user else "libdsim_emu_dyn.so")
-    deps = _sources() + ([p for _, p in USER_MODELS] + [os.path.join(ROOT, "diffrl_amd", "specialise.py")] if user else [])
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + ".tmp%d" % os.getpid()
-        cmd = ["g++"] + CXXFLAGS
-        with tempfile.TemporaryDirectory() as d:
-            if user:
-                from diffrl_amd import specialise
-                from diffrl_amd.template import ArticulationTemplate
-                hdr = os.path.join(d, "dyn_user_layouts.hpp")
-                with open(hdr, "w") as f:
-                    f.write(specialise.render([(tag, ArticulationTemplate.load(p)) for tag, p in USER_MODELS]))
-                cmd += ['-DDSIM_STATIC_LAYOUTS_FILE="%s"' % hdr, "-DDSIM_STATIC_VARIANTS(X)=" + " ".join("X(%s)" % t for t, _ in USER_MODELS)]
-            subprocess.check_call(cmd + ["-shared", "-o", tmp, os.path.join(EMU_DIR, "dsim_emu_dyn.cpp")])
-        os.replace(tmp, so)
-    _libs[user] = C.CDLL(so)
-    return _libs[user]
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _c(a):
-    return np.ascontiguousarray(a, dtype=np.float32) if a is not None else None
-
-
-def _mode(lib, static, waves):
-    lib.dsim_emu_use_static(1 if static else 0)
-    lib.dsim_emu_set_waves(waves)
 
 
 def emu_dyn_forward(t, q, qd, act, mact, static=False, waves=1, user=False):
-    lib = dyn_emu(user)
+    lib = emu_user() if user else emu()
     desc, keep = make_desc(t)
-    q, qd, act, mact = _c(q), _c(qd), _c(act), _c(mact)
+    q, qd, act, mact = f32(q), f32(qd), f32(act), f32(mact)
     N, L = q.shape[0], t.n_links
     tau = np.full((N, t.n_qd), np.nan, np.float32)
     qdd = np.full((N, t.n_qd), np.nan, np.float32)
     fs = np.full((N, L, 6), np.nan, np.float32)
-    _mode(lib, static, waves)
-    rc = lib.dsim_emu_joint_dynamics(C.byref(desc), C.c_int(N), _p(q), _p(qd), _p(act), _p(mact), _p(tau), _p(qdd), _p(fs))
-    _mode(lib, False, 1)
+    with mode(lib, static, waves):
+        rc = lib.dsim_emu_joint_dynamics(C.byref(desc), C.c_int(N), ptr(q), ptr(qd), ptr(act), ptr(mact), ptr(tau), ptr(qdd), ptr(fs))
     assert rc == 0, rc
     return tau, qdd, fs
 
 
 def emu_dyn_backward(t, q, qd, act, mact, gtau, gqdd, gfs, static=False, waves=1, user=False):
     """-> gq, gqd, gact, gmact (None for a model without muscles)"""
-    lib = dyn_emu(user)
+    lib = emu_user() if user else emu()
     desc, keep = make_desc(t)
-    q, qd, act, mact, gtau, gqdd, gfs = _c(q), _c(qd), _c(act), _c(mact), _c(gtau), _c(gqdd), _c(gfs)
+    q, qd, act, mact, gtau, gqdd, gfs = f32(q), f32(qd), f32(act), f32(mact), f32(gtau), f32(gqdd), f32(gfs)
     N = q.shape[0]
     gq = np.full((N, t.n_q), np.nan, np.float32)
     gqd = np.full((N, t.n_qd), np.nan, np.float32)
     gact = np.full((N, t.n_qd), np.nan, np.float32)
     gmact = np.full((N, t.n_muscles), np.nan, np.float32) if t.n_muscles else None
-    _mode(lib, static, waves)
-    rc = lib.dsim_emu_joint_dynamics_backward(C.byref(desc), C.c_int(N), _p(q), _p(qd), _p(act), _p(mact), _p(gtau), _p(gqdd),
-                                              _p(gfs), _p(gq), _p(gqd), _p(gact), _p(gmact))
-    _mode(lib, False, 1)
+    with mode(lib, static, waves):
+        rc = lib.dsim_emu_joint_dynamics_backward(C.byref(desc), C.c_int(N), ptr(q), ptr(qd), ptr(act), ptr(mact), ptr(gtau), ptr(gqdd),
+                                                  ptr(gfs), ptr(gq), ptr(gqd), ptr(gact), ptr(gmact))
     assert rc == 0, rc
     return gq, gqd, gact, gmact
 
@@ -125,23 +75,21 @@ def emu_dyn_backward(t, q, qd, act, mact, gtau, gqdd, gfs, static=False, waves=1
 def emu_step_adjoint(t, q, qd, act, mact, h, gqd_out, static=False, waves=1, user=False):
     """dsim_step_backward of ONE substep of length h with a fresh mass matrix on the host harness, gq_out = 0:
     gq_in = h (d qdd / d q)^T g, gact = h (d qdd / d act)^T g (and gmact likewise) -> (gq_in, gact, gmact | None)"""
-    lib = dyn_emu(user)
+    lib = emu_user() if user else emu()
     desc, keep = make_desc(t)
-    q, qd, act, gqd_out = _c(q), _c(qd), _c(act), _c(gqd_out)
+    q, qd, act, gqd_out = f32(q), f32(qd), f32(act), f32(gqd_out)
     N = q.shape[0]
-    m = _c(mact) if (mact is not None and t.n_muscles) else np.zeros((N, 0), np.float32)
-    _mode(lib, static, waves)
-    lib.dsim_emu_ckpt_floats.restype = C.c_longlong
-    ck = np.zeros((N, int(lib.dsim_emu_ckpt_floats(C.byref(desc), C.c_int(1), C.c_int(1)))), np.float32)
-    qo, qdo = np.zeros_like(q), np.zeros_like(qd)
-    rc = lib.dsim_emu_step_forward(C.byref(desc), C.c_int(N), _p(q), _p(qd), _p(act), _p(m), C.c_float(h), C.c_int(1), C.c_int(1),
-                                   _p(qo), _p(qdo), _p(ck))
-    assert rc == 0, rc
-    gq_out = np.zeros_like(q)
-    gq, gqd, ga, gm = np.zeros_like(q), np.zeros_like(qd), np.zeros_like(act), np.zeros_like(m)
-    rc = lib.dsim_emu_step_backward(C.byref(desc), C.c_int(N), _p(ck), _p(act), _p(m), C.c_float(h), C.c_int(1), C.c_int(1),
-                                    _p(gq_out), _p(gqd_out), _p(gq), _p(gqd), _p(ga), _p(gm))
-    _mode(lib, False, 1)
+    m = f32(mact) if (mact is not None and t.n_muscles) else np.zeros((N, 0), np.float32)
+    with mode(lib, static, waves):
+        ck = np.zeros((N, int(lib.dsim_emu_ckpt_floats(C.byref(desc), C.c_int(1), C.c_int(1)))), np.float32)
+        qo, qdo = np.zeros_like(q), np.zeros_like(qd)
+        rc = lib.dsim_emu_step_forward(C.byref(desc), C.c_int(N), ptr(q), ptr(qd), ptr(act), ptr(m), C.c_float(h), C.c_int(1), C.c_int(1),
+                                       ptr(qo), ptr(qdo), ptr(ck))
+        assert rc == 0, rc
+        gq_out = np.zeros_like(q)
+        gq, gqd, ga, gm = np.zeros_like(q), np.zeros_like(qd), np.zeros_like(act), np.zeros_like(m)
+        rc = lib.dsim_emu_step_backward(C.byref(desc), C.c_int(N), ptr(ck), ptr(act), ptr(m), C.c_float(h), C.c_int(1), C.c_int(1),
+                                        ptr(gq_out), ptr(gqd_out), ptr(gq), ptr(gqd), ptr(ga), ptr(gm))
     assert rc == 0, rc
     return gq, ga, (gm if t.n_muscles else None)
 

@@ -12,6 +12,7 @@
 
 #define DSIM_FN static inline
 #include "../../diffrl_amd/csrc/dsim_core.hpp"
+#include "../../diffrl_amd/csrc/dsim_abi.hpp"
 #include "../../diffrl_amd/csrc/dsim_literal.hpp"
 #ifdef DSIM_STATIC_LAYOUTS_FILE   // (a generated header with user models: tests/inject/dsim_static_layouts_user.hpp, see the Makefile)
 #include DSIM_STATIC_LAYOUTS_FILE
@@ -220,7 +221,7 @@ template <int NW, int LANES = DSIM_NL> struct HostExecT {
     }
     void mark(int) {}
     void begin_request() {}
-    void begin() {}   // the host image is set up by make_ctx (constants copied, work area zero)
+    void begin() {}   // the host image is set up by emu_ctx (constants copied, work area zero)
     float io_[NL][DSIM_IO_MAX];   // early-load registers of the specialised kernels
     float* io(int lane) { return io_[lane]; }
     float hacc_[NL][DSIM_HACC_MAX];  // what a lane keeps in registers across phases on the GPU
@@ -255,14 +256,19 @@ extern "C" void dsim_emu_set_waves(int w) { g_waves = w > 1 ? 4 : 1; }
 static int g_half = 0;   // 32 lanes per environment (specialised one-wave variants only: the pair kernels)
 extern "C" void dsim_emu_set_half_wave(int on) { g_half = on; }
 
-static void make_ctx(const DsimLayout& lay, std::vector<float>& lds, DsimCtx& c, float h) {
+// The image of one environment on the host: zeros with the model constants copied in (what DevExec::begin leaves in LDS), and
+// the context of the given layout types and checkpoint mode on it.  The one statement of this prologue: every entry point gets
+// its context here -- those that run the kernels' variants through emu_each_env below, the operator-level ones in front of it
+// (always the generic one-wave path, whatever the mode switches say) directly.
+template <bool LEAN = false, class O, class D>
+static DsimCtxT<O, D, LEAN> emu_ctx(const DsimLayout& lay, std::vector<float>& lds, float h, O o, D d) {
     lds.assign(lay.o.total_words, 0.f);
     memcpy(lds.data(), lay.cblob.data(), sizeof(uint32_t) * lay.o.const_words);
-    c.s = lds.data(); c.k = c.s;
-    c.o = lay.o;
-    c.d = lay.d;
-    c.h = h;
+    DsimCtxT<O, D, LEAN> c;
+    c.s = lds.data(); c.k = c.s; c.o = o; c.d = d; c.h = h;
+    return c;
 }
+static DsimCtx emu_ctx(const DsimLayout& lay, std::vector<float>& lds, float h) { return emu_ctx(lay, lds, h, lay.o, lay.d); }
 
 extern "C" {
 
@@ -283,8 +289,7 @@ int dsim_emu_substep_image(const dsim_model_desc* m, const float* q, const float
     DsimLayout lay;
     if (!dsim_build_layout(*m, lay).empty()) return -1;
     std::vector<float> lds;
-    DsimCtx c;
-    make_ctx(lay, lds, c, h);
+    DsimCtx c = emu_ctx(lay, lds, h);
     memcpy(lds.data() + lay.o.q, q, 4 * lay.d.nq);
     memcpy(lds.data() + lay.o.qd, qd, 4 * lay.d.nd);
     memcpy(lds.data() + lay.o.act, act, 4 * lay.d.nd);
@@ -308,8 +313,7 @@ int dsim_emu_step_forward(const dsim_model_desc* m, int n_envs, const float* q_i
     HostExec ex;
     for (int e = 0; e < n_envs; ++e) {
         std::vector<float> lds;
-        DsimCtx c;
-        make_ctx(lay, lds, c, dt / float(substeps));
+        DsimCtx c = emu_ctx(lay, lds, dt / float(substeps));
         dsim_sim_step_forward(c, ex, substeps, mm_freq, q_in + (size_t)e * nq, qd_in + (size_t)e * nd,
                               act + (size_t)e * nd, M ? mact + (size_t)e * M : nullptr, q_out + (size_t)e * nq,
                               qd_out + (size_t)e * nd, ckpt ? ckpt + (size_t)e * dsim_ckpt_words(lay.o.save_words, nq, nd, substeps, mm_freq) : nullptr);
@@ -327,8 +331,7 @@ extern "C" int dsim_emu_step_backward(const dsim_model_desc* m, int n_envs, cons
     HostExec ex;
     for (int e = 0; e < n_envs; ++e) {
         std::vector<float> lds;
-        DsimCtx c;
-        make_ctx(lay, lds, c, dt / float(substeps));
+        DsimCtx c = emu_ctx(lay, lds, dt / float(substeps));
         dsim_sim_step_backward(c, ex, substeps, mm_freq, ckpt + (size_t)e * dsim_ckpt_words(lay.o.save_words, nq, nd, substeps, mm_freq), act + (size_t)e * nd,
                                M ? mact + (size_t)e * M : nullptr, gq_out + (size_t)e * nq, gqd_out + (size_t)e * nd,
                                gq_in + (size_t)e * nq, gqd_in + (size_t)e * nd, gact ? gact + (size_t)e * nd : nullptr,
@@ -356,8 +359,7 @@ extern "C" int dsim_emu_step_backward_literal(const dsim_model_desc* m, int n_en
     cc.d = lay.d;
     for (int e = 0; e < n_envs; ++e) {
         std::vector<float> lds;
-        DsimCtx c;
-        make_ctx(lay, lds, c, dt / float(substeps));
+        DsimCtx c = emu_ctx(lay, lds, dt / float(substeps));
         const float* row = ckpt + (size_t)e * stride;
         dsim_sim_step_backward(c, ex, substeps, mm_freq, row, act + (size_t)e * nd, M ? mact + (size_t)e * M : nullptr,
                                gq_out + (size_t)e * nq, gqd_out + (size_t)e * nd, gq_in + (size_t)e * nq, gqd_in + (size_t)e * nd,
@@ -395,17 +397,6 @@ extern "C" int dsim_emu_literal_tangents(const dsim_model_desc* m, const float* 
 }
 
 // ---- fused env surface (host lane-serial) ----
-static DsimEnvSpec to_spec(const dsim_env_spec* e) {
-    DsimEnvSpec sp;
-    sp.kind = e->kind; sp.rew_kind = e->rew_kind; sp.n_act = e->n_act; sp.n_obs = e->n_obs;
-    sp.act_offset = e->act_offset; sp.act_muscle = e->act_muscle; sp.obs_actions = e->obs_actions; sp.sanitize = e->sanitize_grads;
-    for (int k = 0; k < 4; ++k) { sp.isr[k] = e->inv_start_rot[k]; sp.pen[k] = e->cartpole_penalties[k]; }
-    sp.tgt_x = e->target_x; sp.tgt_z = e->target_z; sp.term_h = e->termination_height;
-    sp.term_tol = e->termination_tolerance; sp.h_scale = e->height_rew_scale; sp.act_pen = e->action_penalty;
-    sp.vel_scale = e->joint_vel_obs_scaling; sp.act_scale = e->act_scale;
-    return sp;
-}
-
 // The per-model specialised code paths (compile-time layouts: `if constexpr (DsimIsStatic...)` branches, bounded sums)
 // can be exercised on the host too: with dsim_emu_use_static(1) the env entry points below instantiate the phase code
 // with the generated all-constexpr layout of the matching model, exactly as the library's dispatch() does.
@@ -439,19 +430,18 @@ template <class F> static int emu_dispatch(const DsimLayout& lay, F&& f) {
     return -2;  // no specialised variant for this model
 }
 
-static DsimEpisode to_episode(const dsim_episode* episode) {
-    DsimEpisode ep{};
-    if (episode) {
-        ep.progress = reinterpret_cast<long long*>(episode->progress);
-        ep.done = reinterpret_cast<long long*>(episode->done);
-        ep.obs_before = episode->obs_before_reset;
-        ep.reset_q = episode->reset_q; ep.reset_qd = episode->reset_qd; ep.reset_count = episode->reset_count;
-        ep.pool = episode->reset_pool; ep.episode_length = episode->episode_length;
-        ep.height_terminate = episode->height_terminate; ep.check_invalid = episode->check_invalid;
-        ep.noise_q = episode->noise_q; ep.noise_qd = episode->noise_qd; ep.noise_angle = episode->noise_angle;
-        ep.seed = episode->seed;
-    }
-    return ep;
+// f(c, ex, e) for e = 0 .. n_envs - 1 with a fresh image each (emu_ctx) in the layout types, wave count and checkpoint mode the
+// switches above select -- the host form of "one environment per workgroup".  CKPT_MODES = false: an entry point without checkpoints
+// (the read-outs, which have no lean variant on the device either) always gets the full-checkpoint context.
+template <bool CKPT_MODES = true, class F> static int emu_each_env(const DsimLayout& lay, int n_envs, float h, F&& f) {
+    return emu_dispatch(lay, [&](auto o, auto d, auto& ex, auto lean) {
+        std::vector<float> lds;
+        for (int e = 0; e < n_envs; ++e) {
+            auto c = emu_ctx<CKPT_MODES && decltype(lean)::value>(lay, lds, h, o, d);
+            f(c, ex, e);
+        }
+        return 0;
+    });
 }
 
 extern "C" int dsim_emu_env_forward(const dsim_model_desc* m, const dsim_env_spec* env, int n_envs, const float* q_in,
@@ -461,21 +451,14 @@ extern "C" int dsim_emu_env_forward(const dsim_model_desc* m, const dsim_env_spe
     DsimLayout lay;
     if (!dsim_build_layout(*m, lay).empty()) return -1;
     const int nq = lay.d.nq, nd = lay.d.nd;
-    DsimEnvSpec sp = to_spec(env);
-    DsimEpisode ep = to_episode(episode);
+    DsimEnvSpec sp = dsim_env_spec_copy(*env);
+    DsimEpisode ep = episode ? dsim_episode_copy(*episode) : DsimEpisode{};
     const size_t stride = dsim_ckpt_words(emu_row(lay), nq, nd, substeps, mm_freq);
-    return emu_dispatch(lay, [&](auto o, auto d, auto& ex, auto lean) {
-        for (int e = 0; e < n_envs; ++e) {
-            std::vector<float> lds(lay.o.total_words, 0.f);
-            memcpy(lds.data(), lay.cblob.data(), sizeof(uint32_t) * lay.o.const_words);
-            DsimCtxT<decltype(o), decltype(d), decltype(lean)::value> c;
-            c.s = lds.data(); c.k = c.s; c.o = o; c.d = d; c.h = dt / float(substeps);
-            dsim_env_fused_forward(c, ex, sp, substeps, mm_freq, q_in + (size_t)e * nq, qd_in + (size_t)e * nd,
-                                   actions + (size_t)e * sp.n_act, q_out + (size_t)e * nq, qd_out + (size_t)e * nd,
-                                   obs + (size_t)e * sp.n_obs, rew + e, ckpt ? ckpt + (size_t)e * stride : nullptr, ep, e,
-                                   n_envs);
-        }
-        return 0;
+    return emu_each_env(lay, n_envs, dt / float(substeps), [&](auto& c, auto& ex, int e) {
+        dsim_env_fused_forward(c, ex, sp, substeps, mm_freq, q_in + (size_t)e * nq, qd_in + (size_t)e * nd,
+                               actions + (size_t)e * sp.n_act, q_out + (size_t)e * nq, qd_out + (size_t)e * nd,
+                               obs + (size_t)e * sp.n_obs, rew + e, ckpt ? ckpt + (size_t)e * stride : nullptr, ep, e,
+                               n_envs);
     });
 }
 
@@ -486,22 +469,15 @@ extern "C" int dsim_emu_env_backward(const dsim_model_desc* m, const dsim_env_sp
     DsimLayout lay;
     if (!dsim_build_layout(*m, lay).empty()) return -1;
     const int nq = lay.d.nq, nd = lay.d.nd;
-    DsimEnvSpec sp = to_spec(env);
+    DsimEnvSpec sp = dsim_env_spec_copy(*env);
     const size_t stride = dsim_ckpt_words(emu_row(lay), nq, nd, substeps, mm_freq);
-    return emu_dispatch(lay, [&](auto o, auto d, auto& ex, auto lean) {
-        for (int e = 0; e < n_envs; ++e) {
-            std::vector<float> lds(lay.o.total_words, 0.f);
-            memcpy(lds.data(), lay.cblob.data(), sizeof(uint32_t) * lay.o.const_words);
-            DsimCtxT<decltype(o), decltype(d), decltype(lean)::value> c;
-            c.s = lds.data(); c.k = c.s; c.o = o; c.d = d; c.h = dt / float(substeps);
-            dsim_env_fused_backward(c, ex, sp, substeps, mm_freq, ckpt + (size_t)e * stride,
-                                    actions + (size_t)e * sp.n_act, gq_out ? gq_out + (size_t)e * nq : nullptr,
-                                    gqd_out ? gqd_out + (size_t)e * nd : nullptr,
-                                    gobs ? gobs + (size_t)e * sp.n_obs : nullptr, grew ? grew + e : nullptr,
-                                    gobs_before ? gobs_before + (size_t)e * sp.n_obs : nullptr, gq_in + (size_t)e * nq,
-                                    gqd_in + (size_t)e * nd, gactions + (size_t)e * sp.n_act);
-        }
-        return 0;
+    return emu_each_env(lay, n_envs, dt / float(substeps), [&](auto& c, auto& ex, int e) {
+        dsim_env_fused_backward(c, ex, sp, substeps, mm_freq, ckpt + (size_t)e * stride,
+                                actions + (size_t)e * sp.n_act, gq_out ? gq_out + (size_t)e * nq : nullptr,
+                                gqd_out ? gqd_out + (size_t)e * nd : nullptr,
+                                gobs ? gobs + (size_t)e * sp.n_obs : nullptr, grew ? grew + e : nullptr,
+                                gobs_before ? gobs_before + (size_t)e * sp.n_obs : nullptr, gq_in + (size_t)e * nq,
+                                gqd_in + (size_t)e * nd, gactions + (size_t)e * sp.n_act);
     });
 }
 
@@ -510,3 +486,8 @@ extern "C" long long dsim_emu_ckpt_floats(const dsim_model_desc* m, int substeps
     if (!dsim_build_layout(*m, lay).empty()) return -1;
     return dsim_ckpt_words(emu_row(lay), lay.d.nq, lay.d.nd, substeps, mm_freq);
 }
+
+// the read-outs and the step Jacobian: entry points of the same harness, kept in files of their own
+#include "dsim_emu_kin.cpp"
+#include "dsim_emu_dyn.cpp"
+#include "dsim_emu_jac.cpp"

@@ -1,33 +1,18 @@
 // dsim_emu_jac.cpp -- TEST-ONLY: the step Jacobian (dsim_core.hpp: dsim_multi_slot around dsim_sim_step_backward) on the
 // lane-serial host executor of dsim_emu.cpp, generic and specialised layouts, one or four wavefronts per environment, full or
-// lean checkpoints (dsim_emu_use_static / dsim_emu_set_waves / dsim_emu_set_ckpt_lean of that file).  Built by tests/jac_lib.py
-// with the flags of tests/emu/Makefile; like dsim_emu.cpp it is not part of the library.  The multi entry points walk the block
+// lean checkpoints (dsim_emu_use_static / dsim_emu_set_waves / dsim_emu_set_ckpt_lean of that file).  Included at the end
+// of dsim_emu.cpp (one translation unit, tests/emu/Makefile); like that file it is not part of the library.  The multi entry points walk the block
 // indices of the device launch, 0 .. n_envs * n_cot - 1, and take every pointer from dsim_multi_slot -- the code the kernels
 // run; the single-sweep entry points do their own per-environment pointer arithmetic, as dsim_bwd_kernel does.
-#include "dsim_emu.cpp"
-
-template <class O, class D, bool LEAN> static DsimCtxT<O, D, LEAN> jac_ctx(const DsimLayout& lay, std::vector<float>& lds, O o, D d, float h) {
-    lds.assign(lay.o.total_words, 0.f);
-    memcpy(lds.data(), lay.cblob.data(), sizeof(uint32_t) * lay.o.const_words);
-    DsimCtxT<O, D, LEAN> c;
-    c.s = lds.data(); c.k = c.s; c.o = o; c.d = d; c.h = h;
-    return c;
-}
-
 extern "C" int dsim_emu_jac_forward(const dsim_model_desc* m, int n_envs, const float* q_in, const float* qd_in, const float* act,
                                     const float* mact, float dt, int substeps, int mm_freq, float* q_out, float* qd_out, float* ckpt) {
     DsimLayout lay;
     if (!dsim_build_layout(*m, lay).empty()) return -1;
     const size_t nq = lay.d.nq, nd = lay.d.nd, M = lay.d.M;
     const size_t stride = dsim_ckpt_words(emu_row(lay), lay.d.nq, lay.d.nd, substeps, mm_freq);
-    return emu_dispatch(lay, [&](auto o, auto d, auto& ex, auto lean) {
-        for (size_t e = 0; e < (size_t)n_envs; ++e) {
-            std::vector<float> lds;
-            auto c = jac_ctx<decltype(o), decltype(d), decltype(lean)::value>(lay, lds, o, d, dt / float(substeps));
-            dsim_sim_step_forward(c, ex, substeps, mm_freq, q_in + e * nq, qd_in + e * nd, act + e * nd, M ? mact + e * M : nullptr,
-                                  q_out + e * nq, qd_out + e * nd, ckpt + e * stride);
-        }
-        return 0;
+    return emu_each_env(lay, n_envs, dt / float(substeps), [&](auto& c, auto& ex, int e) {
+        dsim_sim_step_forward(c, ex, substeps, mm_freq, q_in + e * nq, qd_in + e * nd, act + e * nd, M ? mact + e * M : nullptr,
+                              q_out + e * nq, qd_out + e * nd, ckpt + e * stride);
     });
 }
 
@@ -38,30 +23,20 @@ extern "C" int dsim_emu_jac_backward(const dsim_model_desc* m, int n_envs, const
     if (!dsim_build_layout(*m, lay).empty()) return -1;
     const size_t nq = lay.d.nq, nd = lay.d.nd, M = lay.d.M;
     const size_t stride = dsim_ckpt_words(emu_row(lay), lay.d.nq, lay.d.nd, substeps, mm_freq);
-    return emu_dispatch(lay, [&](auto o, auto d, auto& ex, auto lean) {
-        for (size_t e = 0; e < (size_t)n_envs; ++e) {
-            std::vector<float> lds;
-            auto c = jac_ctx<decltype(o), decltype(d), decltype(lean)::value>(lay, lds, o, d, dt / float(substeps));
-            dsim_sim_step_backward(c, ex, substeps, mm_freq, ckpt + e * stride, act + e * nd, M ? mact + e * M : nullptr,
-                                   gq_out + e * nq, gqd_out + e * nd, gq_in + e * nq, gqd_in + e * nd, gact ? gact + e * nd : nullptr,
-                                   (gmact && M) ? gmact + e * M : nullptr);
-        }
-        return 0;
+    return emu_each_env(lay, n_envs, dt / float(substeps), [&](auto& c, auto& ex, int e) {
+        dsim_sim_step_backward(c, ex, substeps, mm_freq, ckpt + e * stride, act + e * nd, M ? mact + e * M : nullptr,
+                               gq_out + e * nq, gqd_out + e * nd, gq_in + e * nq, gqd_in + e * nd, gact ? gact + e * nd : nullptr,
+                               (gmact && M) ? gmact + e * M : nullptr);
     });
 }
 
 // the device launch of dsim_bwd_multi_kernel, block by block
 static int jac_run_multi(const DsimLayout& lay, int n_envs, float dt, int substeps, int mm_freq, DsimMultiArgs a) {
     a.ckpt_stride = (long long)dsim_ckpt_words(emu_row(lay), lay.d.nq, lay.d.nd, substeps, mm_freq);
-    return emu_dispatch(lay, [&](auto o, auto d, auto& ex, auto lean) {
-        for (int b = 0; b < n_envs * a.n_cot; ++b) {
-            std::vector<float> lds;
-            auto c = jac_ctx<decltype(o), decltype(d), decltype(lean)::value>(lay, lds, o, d, dt / float(substeps));
-            const DsimMultiSlot s = dsim_multi_slot(a, b, c.d.nd, c.d.M);
-            dsim_sim_step_backward(c, ex, substeps, mm_freq, s.ckpt, s.act, s.mact, s.gq_out, s.gqd_out, s.gq_in, s.gqd_in, s.gact,
-                                   s.gmact);
-        }
-        return 0;
+    return emu_each_env(lay, n_envs * a.n_cot, dt / float(substeps), [&](auto& c, auto& ex, int b) {
+        const DsimMultiSlot s = dsim_multi_slot(a, b, c.d.nd, c.d.M);
+        dsim_sim_step_backward(c, ex, substeps, mm_freq, s.ckpt, s.act, s.mact, s.gq_out, s.gqd_out, s.gq_in, s.gqd_in, s.gact,
+                               s.gmact);
     });
 }
 

@@ -1,7 +1,7 @@
 """Test infrastructure of the step Jacobian (dsim_step_backward_multi / dsim_step_jacobian):
 
-* the lane-serial host build of the block mapping (dsim_core.hpp: dsim_multi_slot) around the step adjoint
-  (tests/emu/dsim_emu_jac.cpp), compiled here with the flags of tests/emu/Makefile;
+* the entry points of the lane-serial host harness for the block mapping (dsim_core.hpp: dsim_multi_slot) around the step
+  adjoint (tests/emu/dsim_emu_jac.cpp; tests/emu_lib.py loads the harness);
 * the comparison against tests/golden/<env>_lin.npz (tools/gen_linearise_golden.py), shared by the host and the GPU tier.
 
 Bounds.  Every Jacobian block (J_qq, J_q_qd, J_qd_q, J_qd_qd, J_act, J_muscle) is compared in ITS OWN max-norm relative error,
@@ -16,79 +16,31 @@ blocks over the threshold, the noisiest one is excluded and the others are compa
   ant, humanoid, hopper, cheetah: every block <= 9.5e-6, nothing excluded.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from diffrl_amd.capi import make_desc
-from kin_lib import CXXFLAGS, ENVS, waves_of  # noqa: F401
+from emu_lib import f32, ptr, emu, mode
+from kin_lib import ENVS, waves_of  # noqa: F401
 from oracle_lib import golden, project_tangent, template_from_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "diffrl_amd", "csrc")
 BOUND, EXCLUDE, MAX_EXCLUDED = 1e-3, 1e-4, 1
 RADIAL = 1e-4   # |J[:, quaternion block] . quat_in| <= RADIAL * max |J|: the step tests' own radial bound
 BLOCKS = ("J_qq", "J_q_qd", "J_qd_q", "J_qd_qd", "J_act", "J_muscle")
-_lib = None
 _cases = {}
-
-
-def jac_emu():
-    global _lib
-    if _lib is not None:
-        return _lib
-    so = os.path.join(EMU_DIR, "libdsim_emu_jac.so")
-    deps = [os.path.join(EMU_DIR, f) for f in ("dsim_emu_jac.cpp", "dsim_emu.cpp")] + \
-           [os.path.join(CSRC, f) for f in ("dsim_core.hpp", "dsim_math.hpp", "dsim_layout.hpp", "dsim_static_layouts.hpp",
-                                            "dsim_literal.hpp")] + [os.path.join(ROOT, "include", "dsim.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + ".tmp%d" % os.getpid()
-        subprocess.check_call(["g++"] + CXXFLAGS + ["-shared", "-o", tmp, os.path.join(EMU_DIR, "dsim_emu_jac.cpp")])
-        os.replace(tmp, so)
-    _lib = C.CDLL(so)
-    _lib.dsim_emu_ckpt_floats.restype = C.c_longlong
-    return _lib
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _c(a):
-    return np.ascontiguousarray(a, dtype=np.float32) if a is not None else None
-
-
-class _Mode:
-    def __init__(self, static, waves, lean=False):
-        self.args = (static, waves, lean)
-
-    def __enter__(self):
-        lib, (static, waves, lean) = jac_emu(), self.args
-        lib.dsim_emu_use_static(1 if static else 0)
-        lib.dsim_emu_set_waves(waves)
-        lib.dsim_emu_set_ckpt_lean(1 if lean else 0)
-        return lib
-
-    def __exit__(self, *exc):
-        lib = jac_emu()
-        lib.dsim_emu_use_static(0)
-        lib.dsim_emu_set_waves(1)
-        lib.dsim_emu_set_ckpt_lean(0)
 
 
 def emu_forward(t, q, qd, act, mact, dt, S, mm, static=False, waves=1, lean=False):
     """-> (q_out, qd_out, ckpt)"""
     desc, keep = make_desc(t)
-    q, qd, act = _c(q), _c(qd), _c(act)
+    q, qd, act = f32(q), f32(qd), f32(act)
     N = q.shape[0]
-    mact = _c(mact) if t.n_muscles else None
-    with _Mode(static, waves, lean) as lib:
+    mact = f32(mact) if t.n_muscles else None
+    with mode(emu(), static, waves, lean) as lib:
         ck = np.zeros((N, int(lib.dsim_emu_ckpt_floats(C.byref(desc), C.c_int(S), C.c_int(mm)))), np.float32)
         qo, qdo = np.zeros_like(q), np.zeros_like(qd)
-        rc = lib.dsim_emu_jac_forward(C.byref(desc), C.c_int(N), _p(q), _p(qd), _p(act), _p(mact), C.c_float(dt), C.c_int(S), C.c_int(mm),
-                                      _p(qo), _p(qdo), _p(ck))
+        rc = lib.dsim_emu_jac_forward(C.byref(desc), C.c_int(N), ptr(q), ptr(qd), ptr(act), ptr(mact), C.c_float(dt), C.c_int(S), C.c_int(mm),
+                                      ptr(qo), ptr(qdo), ptr(ck))
     assert rc == 0, rc
     return qo, qdo, ck
 
@@ -102,13 +54,13 @@ def _outputs(t, shape):
 def emu_backward(t, ck, act, mact, dt, S, mm, gq_out, gqd_out, static=False, waves=1, lean=False):
     """one sweep per environment, the pointer arithmetic of dsim_bwd_kernel -> (gq_in, gqd_in, gact, gmact | None)"""
     desc, keep = make_desc(t)
-    ck, act, gq_out, gqd_out = _c(ck), _c(act), _c(gq_out), _c(gqd_out)
-    mact = _c(mact) if t.n_muscles else None
+    ck, act, gq_out, gqd_out = f32(ck), f32(act), f32(gq_out), f32(gqd_out)
+    mact = f32(mact) if t.n_muscles else None
     N = ck.shape[0]
     out = _outputs(t, (N,))
-    with _Mode(static, waves, lean) as lib:
-        rc = lib.dsim_emu_jac_backward(C.byref(desc), C.c_int(N), _p(ck), _p(act), _p(mact), C.c_float(dt), C.c_int(S), C.c_int(mm),
-                                       _p(gq_out), _p(gqd_out), *[_p(o) for o in out])
+    with mode(emu(), static, waves, lean) as lib:
+        rc = lib.dsim_emu_jac_backward(C.byref(desc), C.c_int(N), ptr(ck), ptr(act), ptr(mact), C.c_float(dt), C.c_int(S), C.c_int(mm),
+                                       ptr(gq_out), ptr(gqd_out), *[ptr(o) for o in out])
     assert rc == 0, rc
     return out
 
@@ -116,15 +68,15 @@ def emu_backward(t, ck, act, mact, dt, S, mm, gq_out, gqd_out, static=False, wav
 def emu_backward_multi(t, ck, act, mact, dt, S, mm, gq_out, gqd_out, shared, static=False, waves=1, lean=False):
     """every block of the device launch through dsim_multi_slot -> (gq_in [N, K, nq], gqd_in, gact, gmact | None)"""
     desc, keep = make_desc(t)
-    ck, act, gq_out, gqd_out = _c(ck), _c(act), _c(gq_out), _c(gqd_out)
-    mact = _c(mact) if t.n_muscles else None
+    ck, act, gq_out, gqd_out = f32(ck), f32(act), f32(gq_out), f32(gqd_out)
+    mact = f32(mact) if t.n_muscles else None
     N, K = ck.shape[0], gq_out.shape[-2]
     assert gq_out.shape == ((K, t.n_q) if shared else (N, K, t.n_q))
     out = _outputs(t, (N, K))
-    with _Mode(static, waves, lean) as lib:
-        rc = lib.dsim_emu_step_backward_multi(C.byref(desc), C.c_int(N), C.c_int(K), C.c_int(1 if shared else 0), _p(ck), _p(act),
-                                              _p(mact), C.c_float(dt), C.c_int(S), C.c_int(mm), _p(gq_out), _p(gqd_out),
-                                              *[_p(o) for o in out])
+    with mode(emu(), static, waves, lean) as lib:
+        rc = lib.dsim_emu_step_backward_multi(C.byref(desc), C.c_int(N), C.c_int(K), C.c_int(1 if shared else 0), ptr(ck), ptr(act),
+                                              ptr(mact), C.c_float(dt), C.c_int(S), C.c_int(mm), ptr(gq_out), ptr(gqd_out),
+                                              *[ptr(o) for o in out])
     assert rc == 0, rc
     return out
 
@@ -132,15 +84,15 @@ def emu_backward_multi(t, ck, act, mact, dt, S, mm, gq_out, gqd_out, shared, sta
 def emu_jacobian(t, ck, act, mact, dt, S, mm, static=False, waves=1, lean=False):
     """-> (J_state [N, K, K], J_act [N, K, nd], J_muscle [N, K, M] | None)"""
     desc, keep = make_desc(t)
-    ck, act = _c(ck), _c(act)
-    mact = _c(mact) if t.n_muscles else None
+    ck, act = f32(ck), f32(act)
+    mact = f32(mact) if t.n_muscles else None
     N, K, M = ck.shape[0], t.n_q + t.n_qd, t.n_muscles
     J = np.full((N, K, K), np.nan, np.float32)
     Ja = np.full((N, K, t.n_qd), np.nan, np.float32)
     Jm = np.full((N, K, M), np.nan, np.float32) if M else None
-    with _Mode(static, waves, lean) as lib:
-        rc = lib.dsim_emu_step_jacobian(C.byref(desc), C.c_int(N), _p(ck), _p(act), _p(mact), C.c_float(dt), C.c_int(S), C.c_int(mm),
-                                        _p(J), _p(Ja), _p(Jm))
+    with mode(emu(), static, waves, lean) as lib:
+        rc = lib.dsim_emu_step_jacobian(C.byref(desc), C.c_int(N), ptr(ck), ptr(act), ptr(mact), C.c_float(dt), C.c_int(S), C.c_int(mm),
+                                        ptr(J), ptr(Ja), ptr(Jm))
     assert rc == 0, rc
     return J, Ja, Jm
 

@@ -1,66 +1,22 @@
 """Test infrastructure of the differentiable body kinematics (dsim_body_kinematics / dsim_body_kinematics_backward):
 
-* the lane-serial host build of the new phase code (tests/emu/dsim_emu_kin.cpp), compiled here with the flags of
-  tests/emu/Makefile, for the shipped layouts and for the two user models of tests/golden/user_*.npz;
+* the entry points of the lane-serial host harness for this phase code (tests/emu/dsim_emu_kin.cpp; tests/emu_lib.py loads the
+  harness), for the shipped layouts and for the two user models of tests/golden/user_*.npz;
 * a float64 numpy statement of the forward kinematics and of the four steps of its adjoint (include/dsim.h, DESIGN.md
   section 3), the reference for models the reference simulator has no recording of.
 """
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from diffrl_amd.capi import make_desc
+from emu_lib import f32, ptr, emu, emu_user, mode
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
-CSRC = os.path.join(ROOT, "diffrl_amd", "csrc")
-CXXFLAGS = ["-O2", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unknown-pragmas",
-            "-Wno-maybe-uninitialized"]   # tests/emu/Makefile
 ENVS = ("ant", "humanoid", "snu", "hopper", "cartpole", "cheetah")
 USER_MODELS = (("UserTree", os.path.join(ROOT, "tests", "golden", "user_tree.npz")),
                ("UserRowTree", os.path.join(ROOT, "tests", "golden", "user_rowtree.npz")))
-_libs = {}
-
-
-def _sources():
-    return [os.path.join(EMU_DIR, f) for f in ("dsim_emu_kin.cpp", "dsim_emu.cpp")] + \
-           [os.path.join(CSRC, f) for f in ("dsim_core.hpp", "dsim_math.hpp", "dsim_layout.hpp", "dsim_static_layouts.hpp",
-                                            "dsim_literal.hpp")] + [os.path.join(ROOT, "include", "dsim.h")]
-
-
-def kin_emu(user=False):
-    """the host harness with the kinematics entry points: shipped layouts, or (user) those of the two user models"""
-    if user in _libs:
-        return _libs[user]
-    so = os.path.join(EMU_DIR, "libdsim_emu_kin_user.so" if user else "libdsim_emu_kin.so")
-    deps = _sources() + ([p for _, p in USER_MODELS] + [os.path.join(ROOT, "diffrl_amd", "specialise.py")] if user else [])
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        tmp = so + ".tmp%d" % os.getpid()
-        cmd = ["g++"] + CXXFLAGS
-        with tempfile.TemporaryDirectory() as d:
-            if user:
-                from diffrl_amd import specialise
-                from diffrl_amd.template import ArticulationTemplate
-                hdr = os.path.join(d, "kin_user_layouts.hpp")
-                with open(hdr, "w") as f:
-                    f.write(specialise.render([(tag, ArticulationTemplate.load(p)) for tag, p in USER_MODELS]))
-                cmd += ['-DDSIM_STATIC_LAYOUTS_FILE="%s"' % hdr, "-DDSIM_STATIC_VARIANTS(X)=" + " ".join("X(%s)" % t for t, _ in USER_MODELS)]
-            subprocess.check_call(cmd + ["-shared", "-o", tmp, os.path.join(EMU_DIR, "dsim_emu_kin.cpp")])
-        os.replace(tmp, so)
-    _libs[user] = C.CDLL(so)
-    return _libs[user]
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p) if a is not None else None
-
-
-def _c(a):
-    return np.ascontiguousarray(a, dtype=np.float32) if a is not None else None
-
 
 def waves_of(t):
     """wavefronts per environment the library picks for this model (dsim_hip.hip: pick_waves)"""
@@ -69,36 +25,29 @@ def waves_of(t):
     return 4 if (d["NS"] > 64 or d["C"] > 64) else 1
 
 
-def _mode(lib, static, waves):
-    lib.dsim_emu_use_static(1 if static else 0)
-    lib.dsim_emu_set_waves(waves)
-
-
 def emu_kin_forward(t, q, qd, static=False, waves=1, user=False, want_xsm=True):
-    lib = kin_emu(user)
+    lib = emu_user() if user else emu()
     desc, keep = make_desc(t)
-    q, qd = _c(q), _c(qd)
+    q, qd = f32(q), f32(qd)
     N, L = q.shape[0], t.n_links
     xsc = np.full((N, L, 7), np.nan, np.float32)
     xsm = np.full((N, L, 7), np.nan, np.float32) if want_xsm else None
     vs = np.full((N, L, 6), np.nan, np.float32) if qd is not None else None
-    _mode(lib, static, waves)
-    rc = lib.dsim_emu_body_kinematics(C.byref(desc), C.c_int(N), _p(q), _p(qd), _p(xsc), _p(xsm), _p(vs))
-    _mode(lib, False, 1)
+    with mode(lib, static, waves):
+        rc = lib.dsim_emu_body_kinematics(C.byref(desc), C.c_int(N), ptr(q), ptr(qd), ptr(xsc), ptr(xsm), ptr(vs))
     assert rc == 0, rc
     return xsc, xsm, vs
 
 
 def emu_kin_backward(t, q, qd, gxsc, gxsm, gvs, static=False, waves=1, user=False):
-    lib = kin_emu(user)
+    lib = emu_user() if user else emu()
     desc, keep = make_desc(t)
-    q, qd, gxsc, gxsm, gvs = _c(q), _c(qd), _c(gxsc), _c(gxsm), _c(gvs)
+    q, qd, gxsc, gxsm, gvs = f32(q), f32(qd), f32(gxsc), f32(gxsm), f32(gvs)
     N = q.shape[0]
     gq = np.full((N, t.n_q), np.nan, np.float32)
     gqd = np.full((N, t.n_qd), np.nan, np.float32) if qd is not None else None
-    _mode(lib, static, waves)
-    rc = lib.dsim_emu_body_kinematics_backward(C.byref(desc), C.c_int(N), _p(q), _p(qd), _p(gxsc), _p(gxsm), _p(gvs), _p(gq), _p(gqd))
-    _mode(lib, False, 1)
+    with mode(lib, static, waves):
+        rc = lib.dsim_emu_body_kinematics_backward(C.byref(desc), C.c_int(N), ptr(q), ptr(qd), ptr(gxsc), ptr(gxsm), ptr(gvs), ptr(gq), ptr(gqd))
     assert rc == 0, rc
     return gq, gqd
 

@@ -306,3 +306,37 @@ def test_non_unit_quaternion_is_reported_by_the_next_call(monkeypatch):
     # argument contract: v_s / gqd if and only if qd
     with pytest.raises(capi.DsimError):
         eng._ck(eng._lib.dsim_body_kinematics(eng._h, 1, None, None, None, None, None, None))
+
+
+@pytest.mark.parametrize("generic", [False, True], ids=["specialised", "generic"])
+@pytest.mark.parametrize("env", K.ENVS)
+def test_body_transforms_is_the_kinematic_read_out_without_qd(env, generic, monkeypatch):
+    """dsim_body_transforms launches the kernel of dsim_body_kinematics (no qd, no v_s, no status words): the same bits as the
+    kinematic read-out, with or without qd.  Three environments: an odd count, one wave each (SNUHumanoid: four)."""
+    t, eng = _engine(env, generic, monkeypatch)
+    g = golden(env + "_step")
+    q, qd = _T(g["q_in"][:3]), _T(g["qd_in"][:3])
+    xf = eng.body_transforms(q)
+    poses = eng.body_kinematics_forward(q, None)
+    full = eng.body_kinematics_forward(q, qd)
+    torch.cuda.synchronize()
+    eng.status()
+    assert xf[0].shape == (3 * t.n_links, 7) and torch.isfinite(xf[0]).all() and torch.isfinite(xf[1]).all()
+    assert torch.equal(xf[0], poses[0]) and torch.equal(xf[1], poses[1])
+    assert torch.equal(xf[0], full[0]) and torch.equal(xf[1], full[1])
+
+
+def test_body_transforms_has_no_precondition_and_the_kinematic_read_out_keeps_its_own(monkeypatch):
+    """a read-back of whatever the caller holds: a non-unit root quaternion is not reported by dsim_body_transforms, and is
+    reported, with its environment, by dsim_body_kinematics on the same kernel"""
+    from diffrl_amd import capi
+    t, eng = _engine("ant", False, monkeypatch)
+    bad = golden("ant_step")["q_in"][:2].copy()
+    bad[1, 3:7] *= np.float32(1.01)
+    eng.body_transforms(_T(bad))
+    torch.cuda.synchronize()
+    eng.status()
+    eng.body_kinematics_forward(_T(bad), None)
+    torch.cuda.synchronize()
+    with pytest.raises(capi.DsimError, match="environment 1"):
+        eng.status()

@@ -73,6 +73,25 @@ def test_rollout_matches_reference(env, name, fused):
     assert relerr(e.state.joint_q.detach().cpu().numpy().reshape(n, -1), g["q_final"]) < 1e-3
 
 
+def test_observe_kernel_on_the_generic_kernels_of_the_muscle_model(monkeypatch):
+    """dsim_env_observe on SNUHumanoid's GENERIC kernels, two environments (the rollouts above launch it on the specialised set):
+    the model whose LDS image needs the opt-in beyond 64 KiB -- the start observation against the recording and the torch path"""
+    monkeypatch.setenv("DSIM_FORCE_GENERIC", "1")
+    g = golden("snu_rollout")
+    dev = torch.device("cuda:0")
+    e = _make("snu", 2, mm=int(g["mm_freq"]))
+    assert e.model.engine().variant == 0
+    e.reset()
+    e.reset_with_state(torch.tensor(g["q0"][:2], device=dev).reshape(-1), torch.tensor(g["qd0"][:2], device=dev).reshape(-1))
+    obs = e.initialize_trajectory().detach().clone()
+    e.fused = False
+    obs_torch = e.initialize_trajectory().detach()
+    keep = g["obs0"].shape[1] - (e.num_actions if getattr(e, "obs_has_actions", False) else 0)
+    assert torch.isfinite(obs).all()
+    assert relerr(obs.cpu().numpy()[:, :keep], g["obs0"][:2, :keep]) < 1e-5
+    assert torch.allclose(obs, obs_torch, rtol=1e-4, atol=1e-5)
+
+
 def test_no_grad_path_and_autoreset():
     """dflex.config.no_grad fast path (no checkpoints) gives the same states; episode_length resets work"""
     g = golden("ant_rollout")
