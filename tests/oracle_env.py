@@ -15,14 +15,16 @@ CLS = {"cartpole": envs.CartPoleSwingUpEnv, "ant": envs.AntEnv, "humanoid": envs
        "snu": envs.SNUHumanoidEnv, "hopper": envs.HopperEnv, "cheetah": envs.CheetahEnv}
 
 
-def make_cpu_env(name, n, template, episode_length=1000, early_termination=False):
+def make_cpu_env(name, n, template, episode_length=1000, early_termination=False, mm_freq=None):
+    """mm_freq: MM_caching_frequency of the environment and of the oracle step (None: the recordings' own, MM[name])"""
+    mm_freq = MM[name] if mm_freq is None else int(mm_freq)
     kw = dict(num_envs=n, device="cpu", render=False, seed=0, episode_length=episode_length, no_grad=False,
-              stochastic_init=False, MM_caching_frequency=MM[name])
+              stochastic_init=False, MM_caching_frequency=mm_freq)
     if name in ("cartpole", "ant", "hopper", "cheetah"):
         kw["early_termination"] = early_termination
     e = CLS[name](**kw)
     e.fused = False
-    t, S, mm, dt = template, SUBSTEPS[name], MM[name], 1.0 / 60.0
+    t, S, mm, dt = template, SUBSTEPS[name], mm_freq, 1.0 / 60.0
 
     class OracleStep(torch.autograd.Function):
         @staticmethod
@@ -52,10 +54,10 @@ def make_cpu_env(name, n, template, episode_length=1000, early_termination=False
     return e
 
 
-def rollout_grad(name, template, q0, qd0, actions):
-    """obs, rew per step and d(-sum rew)/d actions through the torch env surface + oracle"""
+def rollout_grad(name, template, q0, qd0, actions, mm_freq=None):
+    """obs, rew per step and d(-sum rew)/d actions through the torch env surface + oracle (mm_freq: see make_cpu_env)"""
     H, n = actions.shape[0], actions.shape[1]
-    e = make_cpu_env(name, n, template)
+    e = make_cpu_env(name, n, template, mm_freq=mm_freq)
     e.clear_grad()
     e.reset()
     e.reset_with_state(torch.tensor(q0, dtype=torch.float32).reshape(-1), torch.tensor(qd0, dtype=torch.float32).reshape(-1))

@@ -97,6 +97,31 @@ def test_lean_checkpoints_give_the_same_mapping():
         assert all(np.array_equal(g[:, k], o) for g, o in zip(got[:3], one[:3]))
 
 
+@pytest.mark.parametrize("static,label", VARIANTS[1:])   # (the generic layout at these schedules: tests/test_emu_phases.py)
+@pytest.mark.parametrize("mm", [3, 2])
+@pytest.mark.parametrize("name", J.ENVS)
+def test_multi_sweep_equals_single_sweeps_at_uneven_mass_matrix_groups(name, mm, static, label):
+    """the block mapping at S = 7 with groups 3,3,1 and 2,2,2,1 (tests/mm_sched.py): every block reads the inverse of each group and
+    the tail of the ONE checkpoint at the offsets of that schedule -- K = 3 shared cotangent pairs against three single sweeps, bit for bit"""
+    import mm_sched as M
+    c = M.case(name)
+    t, waves = c["t"], J.waves_of(c["t"])
+    a = (c["act"], c["mact"], M.DT, M.S, mm)
+    qo, qdo, ck = J.emu_forward(t, c["q"], c["qd"], *a, static, waves)
+    rng = np.random.default_rng(31)
+    N, K = 2, 3          # (two environments: the block mapping has an environment stride to get wrong, the harness is lane-serial)
+    gq, gqd = rng.normal(size=(K, t.n_q)).astype(np.float32), rng.normal(size=(K, t.n_qd)).astype(np.float32)
+    b = (c["act"][:N], c["mact"][:N] if c["mact"] is not None else None, M.DT, M.S, mm)
+    singles = [J.emu_backward(t, ck[:N], *b, np.repeat(gq[k:k + 1], N, 0), np.repeat(gqd[k:k + 1], N, 0), static, waves) for k in range(K)]
+    want = tuple(np.stack([s[j] for s in singles], axis=1) if singles[0][j] is not None else None for j in range(4))
+    got = J.emu_backward_multi(t, ck[:N], *b, gq, gqd, True, static, waves)
+    assert all(g is None or np.isfinite(g).all() for g in got)
+    assert _eq(got, want)
+    # and the sweep is the adjoint of this schedule, not only consistent with itself: all six states against the oracle
+    one = J.emu_backward(t, ck, *a, c["gq"], c["gqd"], static, waves)
+    M.assert_step(name, mm, dict(q=qo, qd=qdo, gq=one[0], gqd=one[1], gact=one[2], gmact=one[3]), label="host " + label)
+
+
 def test_binding_names_both_calls():
     assert "dsim_step_backward_multi" in capi.EXPORTS and "dsim_step_jacobian" in capi.EXPORTS
     assert capi.EXPECTED_ABI == 110
