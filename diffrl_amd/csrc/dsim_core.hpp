@@ -2675,35 +2675,9 @@ DSIM_FN void dsim_body_kin_forward(const Ctx& c, Exec& ex, const float* g_q, con
 //      adj q = S . Wt; ball 2 (t, 0) (x) q with t_k = S_k . Wt; free R_j^T f and 2 (R_j^T (tau - p_c x f), 0) (x) q_r.
 // Cotangent pointers may be null (= zeros).  Every word of g_gq (and g_gqd) is WRITTEN by the lane of the link that owns it:
 // no atomics, the result does not depend on the launch.  The quaternion blocks of g_gq have no component along the quaternion.
-template <class Ctx, class Exec>
-DSIM_FN void dsim_body_kin_backward(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, const float* g_gxsc,
-                                    const float* g_gxsm, const float* g_gvs, float* g_gq, float* g_gqd) {
-    dsim_body_kin_load(c, ex, g_q, g_qd);
-    dsim_fwd_kinematics(c, ex);
-    ex.run([&](int lane) {
-        for (int i = lane; i < c.d.L; i += Exec::NL) {
-            const v3 p = ld3(WF(xsc) + 7 * i);
-            const q4 r = ldq(WF(xsc) + 7 * i + 3);
-            v3 f = zero3(), tau = zero3();
-            q4 gr = mkq(0.f, 0.f, 0.f, 0.f);
-            if (g_gxsc) {
-                const v3 gp = ld3(g_gxsc + 7 * i);
-                f += gp;
-                tau += cross(p, gp);
-                gr += ldq(g_gxsc + 7 * i + 3);
-            }
-            if (g_gxsm) {
-                const v3 pm = rotate(r, ld3(CF(com) + 3 * i)) + p;
-                const v3 gp = ld3(g_gxsm + 7 * i);
-                f += gp;
-                tau += cross(pm, gp);
-                gr += ldq(g_gxsm + 7 * i + 3);
-            }
-            tau += qvec(qmul(gr, qconj(r))) * 0.5f;
-            stsv(WF(aw) + 6 * i, mksv(tau, f));
-            stsv(WF(av) + 6 * i, g_gvs ? ldsv(g_gvs + 6 * i) : zerosv());
-        }
-    });
+// Steps 2 - 4 of this reverse pass as a helper of their own, entered with the links' pose wrenches in aw and twist cotangents in av (shared with
+// dsim_ground_contact_backward).
+template <class Ctx, class Exec> DSIM_FN void dsim_body_kin_backward_tail(const Ctx& c, Exec& ex, float* g_gq, float* g_gqd) {
     ex.run([&](int lane) {
         for (int it = lane; it < 6 * c.d.L; it += Exec::NL) {
             const int i = it / 6, k = it - 6 * i;
@@ -2762,6 +2736,179 @@ DSIM_FN void dsim_body_kin_backward(const Ctx& c, Exec& ex, const float* g_q, co
             }
         }
     });
+}
+template <class Ctx, class Exec>
+DSIM_FN void dsim_body_kin_backward(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, const float* g_gxsc,
+                                    const float* g_gxsm, const float* g_gvs, float* g_gq, float* g_gqd) {
+    dsim_body_kin_load(c, ex, g_q, g_qd);
+    dsim_fwd_kinematics(c, ex);
+    ex.run([&](int lane) {
+        for (int i = lane; i < c.d.L; i += Exec::NL) {
+            const v3 p = ld3(WF(xsc) + 7 * i);
+            const q4 r = ldq(WF(xsc) + 7 * i + 3);
+            v3 f = zero3(), tau = zero3();
+            q4 gr = mkq(0.f, 0.f, 0.f, 0.f);
+            if (g_gxsc) {
+                const v3 gp = ld3(g_gxsc + 7 * i);
+                f += gp;
+                tau += cross(p, gp);
+                gr += ldq(g_gxsc + 7 * i + 3);
+            }
+            if (g_gxsm) {
+                const v3 pm = rotate(r, ld3(CF(com) + 3 * i)) + p;
+                const v3 gp = ld3(g_gxsm + 7 * i);
+                f += gp;
+                tau += cross(pm, gp);
+                gr += ldq(g_gxsm + 7 * i + 3);
+            }
+            tau += qvec(qmul(gr, qconj(r))) * 0.5f;
+            stsv(WF(aw) + 6 * i, mksv(tau, f));
+            stsv(WF(av) + 6 * i, g_gvs ? ldsv(g_gvs + 6 * i) : zerosv());
+        }
+    });
+    dsim_body_kin_backward_tail(c, ex, g_gq, g_gqd);
+}
+
+// Differentiable ground-contact read-out of a given (q, qd) (dsim_ground_contacts / dsim_ground_contacts_backward,
+// include/dsim.h): per contact the point tested against the ground, its velocity and the force on it, and per link the sum of
+// the contact wrenches -- what dsim_contact_wrench evaluates every substep and keeps only as the wrench.  The sibling of that
+// function: the same operations in the same order (so `force` and the wrench (p x F, F) carry the step kernels' roundings), with
+// the three intermediate vectors returned.
+struct DsimContactEval {
+    v3 p, dpdt, F;
+};
+DSIM_FN DsimContactEval dsim_contact_eval(const DsimContactConst& k, v3 xp, q4 xq, sv6 vb) {
+    const float ke = k.ke, kd = k.kd, kf = k.kf, mu = k.mu;
+    DsimContactEval ev;
+    v3 p = xp + rotate(xq, k.cp);
+    p.y -= k.cdist;
+    const v3 dpdt = vb.v + cross(vb.w, p);
+    const float cc = p.y;
+    ev.p = p;
+    ev.dpdt = dpdt;
+    ev.F = zero3();
+    if (cc < 0.0f) {
+        const float vn = dpdt.y;
+        const v3 vt = mk3(dpdt.x, 0.f, dpdt.z);
+        const float fn = cc * ke;
+        const float fd = (vn < 0.0f ? vn : 0.0f) * kd * (0.0f - cc);
+        const float vt2 = dot(vt, vt), ilt = dsim_inv_len(vt2), lt = vt2 * ilt;   // (as in dsim_contact_wrench)
+        const float a1 = kf * lt, a2 = 0.0f - mu * cc * ke;
+        const float smin = a1 < a2 ? a1 : a2;
+        const v3 ft = vt * (smin * ilt);
+        ev.F = mk3(ft.x, fn + fd, ft.z);
+    }
+    return ev;
+}
+// The contacts are dealt across the environment's lanes (stride Exec::NL); every value goes from registers to global memory,
+// the wrench rows to cw, from which each link gathers its own in contact order (dsim_body_contact_sum, as the step does).
+// Output pointers may be null (skipped).
+template <class Ctx, class Exec>
+DSIM_FN void dsim_ground_contact_forward(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, float* g_point, float* g_vel,
+                                         float* g_force, float* g_lw, int* g_status = nullptr, int env = 0) {
+    dsim_body_kin_load(c, ex, g_q, g_qd);
+    dsim_check_unit_quats(c, ex, g_status, env);
+    dsim_fwd_kinematics(c, ex);
+    if (c.d.C > 0) {
+        ex.run([&](int lane) {
+            for (int k = lane; k < c.d.C; k += Exec::NL) {
+                const int b = CI(cbody)[k];
+                const DsimContactEval ev = dsim_contact_eval(dsim_contact_load(c, k), ld3(WF(xsc) + 7 * b), ldq(WF(xsc) + 7 * b + 3),
+                                                             ldsv(WF(v) + 6 * b));
+                if (g_point) st3(g_point + 3 * k, ev.p);
+                if (g_vel) st3(g_vel + 3 * k, ev.dpdt);
+                if (g_force) st3(g_force + 3 * k, ev.F);
+                stsv(WF(cw) + 6 * k, mksv(cross(ev.p, ev.F), ev.F));
+            }
+        });
+    }
+    if (g_lw) {
+        ex.run([&](int lane) {
+            for (int it = lane; it < 6 * c.d.L; it += Exec::NL) {
+                const int i = it / 6, k = it - 6 * i;
+                g_lw[it] = c.d.C > 0 ? dsim_body_contact_sum(c, i, WF(cw), 6, k, 0.f) : 0.f;
+            }
+        });
+    }
+}
+// The reverse pass: cotangents (gpoint, gvel, gforce [C][3], glink_wrench [L][6]), each possibly null (= zeros), to cotangents
+// on (q, qd).  The kinematics are re-run; per contact, with A the link-wrench cotangent of its body,
+//   a_F = gforce + A.v + A.w x p and a_p = F x A.w through the force, by the rules of dsim_bwd_external_items_n (nothing where
+//   the contact is inactive, the branches of vn < 0 and a1 < a2 as evaluated, zero gradient of normalize / length at vt = 0);
+//   a_dp += gvel, a_p += gpoint (always), and dpdt = v + w x p gives a_p += a_dp x w;
+//   the body receives the pose wrench (x x a_p, a_p) at the body-fixed point x and the twist cotangent (p x a_dp, a_dp),
+// in the rows acx carries in the step adjoint.  Each link gathers its contacts' rows in contact order into aw and av, and steps
+// 2 - 4 of the kinematic adjoint do the rest.  No atomics; gq and gqd are written.
+template <class Ctx, class Exec>
+DSIM_FN void dsim_ground_contact_backward(const Ctx& c, Exec& ex, const float* g_q, const float* g_qd, const float* g_gpoint,
+                                          const float* g_gvel, const float* g_gforce, const float* g_glw, float* g_gq,
+                                          float* g_gqd) {
+    dsim_body_kin_load(c, ex, g_q, g_qd);
+    dsim_fwd_kinematics(c, ex);
+    if (c.d.C > 0) {
+        ex.run([&](int lane) {
+            for (int k = lane; k < c.d.C; k += Exec::NL) {
+                const int b = CI(cbody)[k];
+                const DsimContactConst cc = dsim_contact_load(c, k);
+                const v3 xp = ld3(WF(xsc) + 7 * b);
+                const q4 xq = ldq(WF(xsc) + 7 * b + 3);
+                const sv6 vb = ldsv(WF(v) + 6 * b);
+                const sv6 A = g_glw ? ldsv(g_glw + 6 * b) : zerosv();
+                const v3 x = xp + rotate(xq, cc.cp);
+                v3 p = x;
+                p.y -= cc.cdist;
+                const float cy = p.y;
+                const v3 dpdt = vb.v + cross(vb.w, p);
+                v3 a_p = g_gpoint ? ld3(g_gpoint + 3 * k) : zero3();
+                v3 a_dp = g_gvel ? ld3(g_gvel + 3 * k) : zero3();
+                if (cy < 0.0f) {
+                    const float ke = cc.ke, kd = cc.kd, kf = cc.kf, mu = cc.mu;
+                    const float vn = dpdt.y;
+                    const v3 vt = mk3(dpdt.x, 0.f, dpdt.z);
+                    const float fn = cy * ke;
+                    const float vmin = vn < 0.0f ? vn : 0.0f;
+                    const float fd = vmin * kd * (0.0f - cy);
+                    const float vt2 = dot(vt, vt), ilt = dsim_inv_len(vt2), lt = vt2 * ilt;   // (as in dsim_contact_wrench)
+                    const float a1 = kf * lt, a2 = 0.0f - mu * cy * ke;
+                    const bool first = a1 < a2;
+                    const float smin = first ? a1 : a2;
+                    const v3 nhat = vt * ilt;
+                    const v3 ft = nhat * smin;
+                    const v3 F = mk3(ft.x, fn + fd, ft.z);
+                    a_p += cross(F, A.w);
+                    v3 a_F = A.v + cross(A.w, p);
+                    if (g_gforce) a_F += ld3(g_gforce + 3 * k);
+                    const float a_fnfd = a_F.y;
+                    const v3 a_ft = a_F;
+                    const float a_s = dot(nhat, a_ft);
+                    const v3 a_nhat = a_ft * smin;
+                    float a_lt = 0.f, a_c = 0.f, a_vn = 0.f;
+                    if (first) a_lt += kf * a_s;
+                    else a_c += -mu * ke * a_s;
+                    const v3 a_vt = (a_nhat - nhat * dot(nhat, a_nhat)) * ilt + nhat * a_lt;
+                    if (vn < 0.0f) a_vn += kd * (0.0f - cy) * a_fnfd;
+                    a_c += -vmin * kd * a_fnfd;
+                    a_c += ke * a_fnfd;
+                    a_vn += -a_vt.y;
+                    a_dp += a_vt;
+                    a_dp.y += a_vn;
+                    a_p.y += a_c;
+                }
+                a_p += cross(a_dp, vb.w);   // dpdt = v + w x p
+                float* o = WF(acx) + 12 * k;
+                stsv(o, mksv(cross(x, a_p), a_p));
+                stsv(o + 6, mksv(cross(p, a_dp), a_dp));
+            }
+        });
+    }
+    ex.run([&](int lane) {
+        for (int it = lane; it < 6 * c.d.L; it += Exec::NL) {
+            const int i = it / 6, k = it - 6 * i;
+            WF(aw)[it] = c.d.C > 0 ? dsim_body_contact_sum(c, i, WF(acx), 12, k, 0.f) : 0.f;
+            WF(av)[it] = c.d.C > 0 ? dsim_body_contact_sum(c, i, WF(acx), 12, 6 + k, 0.f) : 0.f;
+        }
+    });
+    dsim_body_kin_backward_tail(c, ex, g_gq, g_gqd);
 }
 
 // Differentiable dynamic read-out of a given (q, qd, act, muscle_act) (dsim_joint_dynamics / dsim_joint_dynamics_backward,

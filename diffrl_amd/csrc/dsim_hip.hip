@@ -968,6 +968,39 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_joint_dyn_bwd_kernel(KCommo
                             gq + e * nq, gqd + e * nd, gact ? gact + e * nd : nullptr, (gmact && M) ? gmact + e * M : nullptr);
 }
 
+// Differentiable ground-contact read-out (dsim_core.hpp: dsim_ground_contact_forward / dsim_ground_contact_backward): one
+// environment per workgroup, plain launch mode.  The forward kernel needs the forward image only; the adjoint re-runs the
+// kinematics phase and uses the cotangent arrays of the adjoint image.
+template <class O, class D, int NW>
+__global__ __launch_bounds__(DSIM_NL * NW) void dsim_ground_con_kernel(KCommonT<O, D> k, const float* __restrict__ q,
+                                                                     const float* __restrict__ qd, float* point, float* vel,
+                                                                     float* force, float* lw) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, 6, dsim_const_words<O>(), false> ex;
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex);
+    const size_t nq = k.d.nq, nd = k.d.nd, C = k.d.C, L = k.d.L;
+    dsim_ground_contact_forward(c, ex, q + e * nq, qd + e * nd, point ? point + e * 3 * C : nullptr, vel ? vel + e * 3 * C : nullptr,
+                                force ? force + e * 3 * C : nullptr, lw ? lw + e * 6 * L : nullptr, k.status, e);
+}
+
+template <class O, class D, int NW>
+__global__ __launch_bounds__(DSIM_NL * NW) void dsim_ground_con_bwd_kernel(KCommonT<O, D> k, const float* __restrict__ q,
+                                                                         const float* __restrict__ qd, const float* __restrict__ gpoint,
+                                                                         const float* __restrict__ gvel, const float* __restrict__ gforce,
+                                                                         const float* __restrict__ glw, float* gq, float* gqd) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, 6, dsim_const_words<O>(), false> ex;
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    const size_t nq = k.d.nq, nd = k.d.nd, C = k.d.C, L = k.d.L;
+    dsim_ground_contact_backward(c, ex, q + e * nq, qd + e * nd, gpoint ? gpoint + e * 3 * C : nullptr,
+                                 gvel ? gvel + e * 3 * C : nullptr, gforce ? gforce + e * 3 * C : nullptr,
+                                 glw ? glw + e * 6 * L : nullptr, gq + e * nq, gqd + e * nd);
+}
+
 
 thread_local std::string g_err;
 
@@ -1209,6 +1242,8 @@ DSIM_READOUT_FAMILY(dsim_body_kin_kernel, true, true)
 DSIM_READOUT_FAMILY(dsim_body_kin_bwd_kernel, false, false)
 DSIM_READOUT_FAMILY(dsim_joint_dyn_kernel, true, true)
 DSIM_READOUT_FAMILY(dsim_joint_dyn_bwd_kernel, false, false)
+DSIM_READOUT_FAMILY(dsim_ground_con_kernel, true, true)
+DSIM_READOUT_FAMILY(dsim_ground_con_bwd_kernel, false, false)
 #undef DSIM_READOUT_FAMILY
 // dsim_body_transforms: the kinematic read-out without qd and v_s, and without the precondition
 struct dsim_body_xf_family : dsim_body_kin_kernel_family {
@@ -1217,7 +1252,8 @@ struct dsim_body_xf_family : dsim_body_kin_kernel_family {
 // The list of the read-out families: the table below walks it, and launch_readout refuses to compile for a family that is not
 // on it (or derived from one that is), so a kernel cannot be launched without being opted in to its LDS size.
 using dsim_readout_families = std::tuple<dsim_env_obs_kernel_family, dsim_body_kin_kernel_family, dsim_body_kin_bwd_kernel_family,
-                                         dsim_joint_dyn_kernel_family, dsim_joint_dyn_bwd_kernel_family>;
+                                         dsim_joint_dyn_kernel_family, dsim_joint_dyn_bwd_kernel_family,
+                                         dsim_ground_con_kernel_family, dsim_ground_con_bwd_kernel_family>;
 template <class Fam, class... Listed> constexpr bool dsim_readout_listed(std::tuple<Listed...>*) {
     return (std::is_base_of<Listed, Fam>::value || ...);
 }
@@ -1634,6 +1670,26 @@ int dsim_joint_dynamics_backward(const dsim_model* m, int n_envs, const float* q
     if (!q || !qd || !gq || !gqd) return fail(DSIM_ERR_INVALID, "null pointer");
     return launch_readout<dsim_joint_dyn_bwd_kernel_family>(m, n_envs, hip_stream, q, qd, act, muscle_act, gtau, gqdd, gf_s, gq, gqd,
                                                             gact, gmuscle_act);
+}
+
+int dsim_ground_contacts(const dsim_model* m, int n_envs, const float* q, const float* qd, float* point, float* vel, float* force,
+                         float* link_wrench, void* hip_stream) {
+    int rc = check_common(m, n_envs, 1.0f, 1, 1);
+    if (rc) return rc;
+    if (!q || !qd) return fail(DSIM_ERR_INVALID, "null pointer");
+    if (!point && !vel && !force && !link_wrench)
+        return fail(DSIM_ERR_INVALID, "no output: point, vel, force and link_wrench are all null");
+    return launch_readout<dsim_ground_con_kernel_family>(m, n_envs, hip_stream, q, qd, point, vel, force, link_wrench);
+}
+
+int dsim_ground_contacts_backward(const dsim_model* m, int n_envs, const float* q, const float* qd, const float* gpoint,
+                                  const float* gvel, const float* gforce, const float* glink_wrench, float* gq, float* gqd,
+                                  void* hip_stream) {
+    int rc = check_common(m, n_envs, 1.0f, 1, 1);
+    if (rc) return rc;
+    if (!q || !qd || !gq || !gqd) return fail(DSIM_ERR_INVALID, "null pointer");
+    return launch_readout<dsim_ground_con_bwd_kernel_family>(m, n_envs, hip_stream, q, qd, gpoint, gvel, gforce, glink_wrench, gq,
+                                                             gqd);
 }
 
 /* 0 = generic kernels, >0 = index of the specialised variant in use (diagnostics / tests) */

@@ -470,5 +470,25 @@ class Model:
         mact = muscle_activation if muscle_activation is not None else getattr(self, "muscle_activation", None)
         return self.engine().joint_dynamics(state.joint_q, state.joint_qd, act, mact if self.muscle_count > 0 else None)
 
+    def ground_contacts(self, state):
+        """(point [contact_count, 3], vel [contact_count, 3], force [contact_count, 3], link_wrench [link_count, 6]) of
+        state.joint_q / joint_qd, DIFFERENTIABLE in both (Engine.ground_contacts): per ground contact, articulation by
+        articulation in the order of contact_link, the point tested against the ground (point[:, 1] < 0: penetrating), its
+        velocity and the force on it (exactly zero where it does not penetrate), and per link the sum of (point x force, force)
+        over its contacts, the contact part of State.body_f_s.  Foot slip, clearance and ground-reaction terms of a loss
+        back-propagate into the joint state and, through the step that produced it, into the actions; capturable like the steps."""
+        return self.engine().ground_contacts(state.joint_q, state.joint_qd)
+
+    @property
+    def contacts_per_articulation(self):
+        """number of ground contacts of one articulation as the kernels see them (0 without ground or before collide())"""
+        return self.template().n_contacts
+
+    @property
+    def contact_link(self):
+        """[contacts_per_articulation] int64: the link (within its articulation) of each contact slot of ground_contacts().  A
+        fresh host-to-device copy: take it once, outside a graph capture."""
+        return torch.as_tensor(np.asarray(self.template().contact_body, dtype=np.int64), device=self.device)
+
     def flatten(self):
         return [v for v in self.__dict__.values() if torch.is_tensor(v)]

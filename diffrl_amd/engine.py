@@ -221,6 +221,39 @@ class Engine:
                 raise capi.DsimError("state tensors disagree on the number of environments")
         return n
 
+    def ground_contacts(self, q, qd):
+        """(point [n_envs * C, 3], vel [n_envs * C, 3], force [n_envs * C, 3], link_wrench [n_envs * n_links, 6]): per ground
+        contact, in model order, the point tested against the ground (point[:, 1] is the signed depth, negative = penetrating),
+        its velocity and the normal-plus-friction force on it (exactly zero where the depth is >= 0), and per link the sum of
+        (point x force, force) over its contacts -- the contact part of the reference's State.body_f_s -- of the state HANDED IN,
+        differentiable in q and qd (GroundContacts below; one launch forward, one backward)."""
+        return GroundContacts.apply(self, q, qd)
+
+    def ground_contacts_forward(self, q, qd):
+        """dsim_ground_contacts on detached contiguous tensors"""
+        n = self._dyn_check(q, qd, None, None)
+        Cn, L = self.template.n_contacts, self.template.n_links
+        point, vel, force = self._new(n * Cn, 3), self._new(n * Cn, 3), self._new(n * Cn, 3)
+        lw = self._new(n * L, 6)
+        self._call(self._lib.dsim_ground_contacts, self._h, n, _ptr(q), _ptr(qd), _ptr(point), _ptr(vel), _ptr(force), _ptr(lw))
+        return point, vel, force, lw
+
+    def ground_contacts_backward(self, q, qd, gpoint, gvel, gforce, glw):
+        """dsim_ground_contacts_backward: any cotangent may be None (= zeros, no buffer); -> (gq, gqd), flat"""
+        n = self._dyn_check(q, qd, None, None)
+        Cn, L = self.template.n_contacts, self.template.n_links
+        for g, size, name in ((gpoint, n * Cn * 3, "gpoint"), (gvel, n * Cn * 3, "gvel"), (gforce, n * Cn * 3, "gforce"),
+                              (glw, n * L * 6, "glink_wrench")):
+            if g is not None:
+                self._check(g, 1, name)
+                if g.numel() != size:
+                    raise capi.DsimError("%s has the wrong size" % name)
+        gq = self._new(n * self.n_q)
+        gqd = self._new(n * self.n_qd)
+        self._call(self._lib.dsim_ground_contacts_backward, self._h, n, _ptr(q), _ptr(qd), _ptr(gpoint), _ptr(gvel), _ptr(gforce),
+                   _ptr(glw), _ptr(gq), _ptr(gqd))
+        return gq, gqd
+
     def last_substep_q(self, ckpt, substeps):
         """joint_q ENTERING the last substep of the step that wrote `ckpt` (the head of that substep's checkpoint row): what the
         reference's eval_rigid_fk saw when it filled the returned State's body_X_sc (sim.py:2316-2601)."""
@@ -514,6 +547,31 @@ class JointDynamics(torch.autograd.Function):
                                                                   c(gtau), c(gqdd), c(gfs))
         return (None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), gact.view(ctx.shapes[2]) if ctx.has[0] else None,
                 gmact.view(ctx.shapes[3]) if ctx.has[1] else None)
+
+
+class GroundContacts(torch.autograd.Function):
+    """(joint_q, joint_qd) -> (point, vel, force, link_wrench): the ground-contact read-out of a state with its adjoint
+    (dsim_ground_contacts / dsim_ground_contacts_backward); the backward launch re-runs the forward pass on the saved inputs.  The
+    quaternion blocks of the returned joint_q gradient have no component along the quaternion, as SimStep's."""
+
+    @staticmethod
+    def forward(ctx, engine, q, qd):
+        qc, qdc = q.detach().contiguous(), qd.detach().contiguous()
+        out = engine.ground_contacts_forward(qc, qdc)
+        ctx.engine = engine
+        ctx.shapes = (q.shape, qd.shape)
+        ctx.set_materialize_grads(False)   # an output the loss does not read costs no cotangent buffer
+        ctx.save_for_backward(qc, qdc)
+        return out
+
+    @staticmethod
+    def backward(ctx, gpoint, gvel, gforce, glw):
+        if gpoint is None and gvel is None and gforce is None and glw is None:
+            return None, None, None
+        q, qd = ctx.saved_tensors
+        c = lambda g: g.contiguous() if g is not None and g.numel() else None  # noqa: E731
+        gq, gqd = ctx.engine.ground_contacts_backward(q, qd, c(gpoint), c(gvel), c(gforce), c(glw))
+        return None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1])
 
 
 class SimStep(torch.autograd.Function):

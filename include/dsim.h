@@ -283,6 +283,35 @@ int dsim_joint_dynamics_backward(const dsim_model* m, int n_envs, const float* q
                                  float* gq, float* gqd, float* gact /* may be NULL */, float* gmuscle_act /* may be NULL */,
                                  void* hip_stream);
 
+/* Differentiable ground contacts: what the ground does to the robot in a given state, and the reverse pass.  C is the number
+ * of contacts per environment, in model order (dsim_model_desc: contact_body / contact_point / contact_dist / contact_material).
+ *   point [N][C][3]        the point tested against the ground: X_sc(body) o contact_point - n contact_dist with n = +y, so
+ *                          point.y is the signed depth (negative = penetrating);
+ *   vel [N][C][3]          v + w x point of the body's twist (the reference's dpdt);
+ *   force [N][C][3]        normal + damping + friction force on the point (the reference's f_total, sim.py:1137-1206), EXACTLY zero
+ *                          where point.y >= 0, with the roundings of the step kernels (their 1 / |vt|; zero friction at vt = 0);
+ *   link_wrench [N][L][6]  per link the sum, in contact order, of (point x force, force): the contact part of State.body_f_s
+ *                          (torque about the world origin, then force).
+ * q and qd are both required; each output may be NULL (skipped), not all four.  A model without contacts succeeds: link_wrench is
+ * zeros and the [N][0][3] outputs are not touched.
+ * The backward call maps cotangents on the four tensors (each may be NULL = zeros) to cotangents on q and qd, which are WRITTEN,
+ * not accumulated.  It re-runs the forward pass on (q, qd): nothing is kept between the two calls.  Per contact the derivative of
+ * the force is the one the step adjoint uses: nothing where point.y >= 0 (an inactive contact contributes nothing through gforce
+ * or glink_wrench), the damping term only where the normal velocity vn < 0, the friction magnitude by the branch
+ * kf |vt| < mu |fn| as evaluated, and zero gradient of normalize and length at vt = 0.  gpoint and gvel are smooth and always
+ * active.  Pose cotangents are world-frame wrenches: the quaternion blocks of gq have NO component along
+ * the quaternion -- project the reference's literal gradient onto the tangent space before comparing.
+ * Like every call here: device pointers borrowed for the call, launches on the caller's stream, no host synchronisation,
+ * deterministic (no atomics).  Precondition: unit quaternions in q; the forward call checks it like the step functions do (the
+ * NEXT call on the model returns DSIM_ERR_INVALID), the backward call does not check again. */
+int dsim_ground_contacts(const dsim_model* m, int n_envs, const float* q, const float* qd,
+                         float* point, float* vel, float* force, float* link_wrench /* each may be NULL, not all four */,
+                         void* hip_stream);
+int dsim_ground_contacts_backward(const dsim_model* m, int n_envs, const float* q, const float* qd,
+                                  const float* gpoint, const float* gvel, const float* gforce,
+                                  const float* glink_wrench /* each may be NULL = zeros */,
+                                  float* gq, float* gqd, void* hip_stream);
+
 /* ---- fused environment surface -------------------------------------
  * The per-step torch glue of the reference environments -- action clip + scale into joint_act /
  * muscle activations (envs/ant.py:157-163, humanoid.py:188-211, snu_humanoid.py:245-271,
