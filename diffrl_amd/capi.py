@@ -140,6 +140,8 @@ ABI = {
     "dsim_joint_dynamics_backward": (_int, [_vp, _int] + [_vp] * 12),
     "dsim_ground_contacts": (_int, [_vp, _int] + [_vp] * 7),
     "dsim_ground_contacts_backward": (_int, [_vp, _int] + [_vp] * 9),
+    "dsim_mass_matrix": (_int, [_vp, _int] + [_vp] * 5),
+    "dsim_mass_matrix_backward": (_int, [_vp, _int] + [_vp] * 6),
     "dsim_step_backward_multi": (_int, [_vp, _int, _int, _int] + [_vp] * 3 + _step + [_vp] * 7),
     "dsim_step_jacobian": (_int, [_vp, _int] + [_vp] * 3 + _step + [_vp] * 4),
 }

@@ -1995,10 +1995,9 @@ template <class Ctx, class Exec> struct DsimSymFill {
         return DsimIsStatic<Ctx>::value && Exec::NL <= DSIM_NL;
     }();
 };
-// H = J^T M J in composite-rigid-body form + armature, inverted in place (Gauss-Jordan, SPD, no pivoting)
-template <class Ctx, class Exec> DSIM_FN void dsim_fwd_mass(const Ctx& c, Exec& ex) {
+// H = J^T M J in composite-rigid-body form + armature, filled into hinv (dsim_fwd_composite has run) ...
+template <class Ctx, class Exec> DSIM_FN void dsim_mass_fill(const Ctx& c, Exec& ex) {
     const int nd = c.d.nd;
-    dsim_fwd_composite(c, ex);
     if constexpr (DsimSymFill<Ctx, Exec>::value) {
         // H is symmetric: the entries on and above the diagonal are evaluated (nd (nd + 1) / 2 items instead of nd^2: Ant 2 passes
         // of a wavefront instead of 4, Humanoid 7 instead of 12) and stored twice.  The upper triangle is dealt to the lanes as a
@@ -2039,6 +2038,10 @@ template <class Ctx, class Exec> DSIM_FN void dsim_fwd_mass(const Ctx& c, Exec& 
             WF(hinv)[it] = hv;
         }
     });
+}
+// ... and inverted in place (Gauss-Jordan, SPD, no pivoting)
+template <class Ctx, class Exec> DSIM_FN void dsim_mass_invert(const Ctx& c, Exec& ex) {
+    const int nd = c.d.nd;
     // In-place Gauss-Jordan inverse, no pivoting (H is SPD).  Per pivot k: p_j = (j == k ? 1 : H[k][j]) * (1 / H[k][k]);
     // row k <- p; every other row i: H[i][j] <- (j == k ? 0 : H[i][j]) - H[i][k] p_j.
     // Specialised kernels: ONE phase -- lane i keeps row i in registers and the pivot row is broadcast across the
@@ -2067,6 +2070,11 @@ template <class Ctx, class Exec> DSIM_FN void dsim_fwd_mass(const Ctx& c, Exec& 
             });
         }
     }
+}
+template <class Ctx, class Exec> DSIM_FN void dsim_fwd_mass(const Ctx& c, Exec& ex) {
+    dsim_fwd_composite(c, ex);
+    dsim_mass_fill(c, ex);
+    dsim_mass_invert(c, ex);
 }
 
 template <class Ctx, class Exec> DSIM_FN void dsim_fwd_solve(const Ctx& c, Exec& ex) {
@@ -5157,5 +5165,132 @@ DSIM_FN void dsim_env_fused_backward(const Ctx& c, Exec& ex, const DsimEnvSpec& 
             else g += sc * WF(aact)[sp.act_offset + k];
             g_gactions[k] = (a >= -1.0f && a <= 1.0f) ? clean(g) : 0.f;
         });
+    });
+}
+
+// ================================================================================================
+// Differentiable mass matrix read-out (dsim_mass_matrix / dsim_mass_matrix_backward, include/dsim.h)
+// ================================================================================================
+// Of a given q: H [nd][nd] = J^T M J + diag(armature), the matrix a refresh substep inverts (the reference's model.H is without
+// the armature, which it adds inside its factorisation); Hinv [nd][nd], the Gauss-Jordan inverse as dsim_fwd_mass leaves it;
+// S [nd][6], the world-frame motion axes of the dofs (State.joint_S_s).  The kinematics phase on (q, qd = act = 0), the composite
+// inertias and the two halves of dsim_fwd_mass -- the phases of the step kernels, so every kernel variant takes the paths its
+// step kernels take, and the same q gives the same bits as a refresh substep and the dynamic read-out.  No qd, no step length:
+// nothing here depends on them.  ADJ: the adjoint's forward pass also runs the external-force and tau phases of the state at
+// rest, so that the body level finds every forward array it reads as the step adjoint and dsim_joint_dyn_backward leave it.
+template <bool ADJ, class Ctx, class Exec>
+DSIM_FN void dsim_mass_phases(const Ctx& c, Exec& ex, const float* g_q, int* g_status, int env) {
+    ex.begin_request();
+    ex.begin();
+    dsim_init_static(c, ex);
+    ex.run_both([&](int lane) { dsim_topo_init<ADJ>(c, ex, lane); });
+    ex.run([&](int lane) {
+        for (int k = lane; k < c.d.nq; k += Exec::NL) WF(q)[k] = g_q[k];
+        for (int k = lane; k < c.d.nd; k += Exec::NL) {
+            WF(qd)[k] = 0.f;
+            WF(act)[k] = 0.f;
+        }
+        for (int k = lane; k < c.d.M; k += Exec::NL) WF(mact)[k] = 0.f;
+    });
+    if constexpr (!ADJ) dsim_check_unit_quats(c, ex, g_status, env);
+    dsim_fwd_kinematics(c, ex);
+    if constexpr (ADJ) {
+        dsim_fwd_external(c, ex);
+        dsim_fwd_tau(c, ex);
+    }
+    dsim_fwd_composite(c, ex);
+    dsim_mass_fill(c, ex);
+}
+// Output pointers may be null (skipped; the inversion is skipped with Hinv: the branch is uniform over the workgroup).
+template <class Ctx, class Exec>
+DSIM_FN void dsim_mass_forward(const Ctx& c, Exec& ex, const float* g_q, float* g_H, float* g_Hinv, float* g_S,
+                               int* g_status = nullptr, int env = 0) {
+    const int nd = c.d.nd;
+    dsim_mass_phases<false>(c, ex, g_q, g_status, env);
+    ex.run([&](int lane) {
+        if (g_H)
+            for (int it = lane; it < nd * nd; it += Exec::NL) g_H[it] = WF(hinv)[it];
+        if (g_S)
+            for (int it = lane; it < 6 * nd; it += Exec::NL) g_S[it] = WF(S)[it];
+    });
+    if (g_Hinv) {
+        dsim_mass_invert(c, ex);
+        ex.run([&](int lane) {
+            for (int it = lane; it < nd * nd; it += Exec::NL) g_Hinv[it] = WF(hinv)[it];
+        });
+    }
+}
+// The reverse pass: cotangents (gH, gHinv [nd][nd], not necessarily symmetric; gS [nd][6]), each possibly null (= zeros), to the
+// cotangent on q.  The forward phases are re-run (nothing is kept between the calls), with the inversion only if gHinv is given;
+//   1. adj H = gH - Hinv^T gHinv Hinv^T, the rule of the inverse with the kernel's own fp32 Hinv.  T = gHinv Hinv^T is formed in
+//      aH (gHinv is read from global memory); then R = -Hinv^T T, whose entry (i, j) reads COLUMN j of T only: the columns are
+//      taken in blocks that fit the lanes' registers (Exec::io, 8 items per lane), every item of a block is evaluated
+//      and held across the barrier, then written over T (+ gH).  Item (i, j) of a block goes to the lane that follows (i, j - 1)'s:
+//      T[k][j] is read by consecutive lanes at consecutive words, Hinv[k][i] is a broadcast;
+//   2. adj S = gS; adj f = adj tau = adj qdd = 0 (the work arrays start as zeros);
+//   3. dsim_bwd_mass, then the body level this variant's step adjoint uses, as in dsim_joint_dyn_backward: with no force
+//      cotangent it carries the composite-inertia and motion-axis cotangents to the poses and on to q.
+// gq is written, by the lane that owns the word; its quaternion blocks are tangent.  No atomics.
+template <class Ctx, class Exec>
+DSIM_FN void dsim_mass_backward(const Ctx& c, Exec& ex, const float* g_q, const float* g_gH, const float* g_gHinv,
+                                const float* g_gS, float* g_gq) {
+    const int nd = c.d.nd;
+    dsim_mass_phases<true>(c, ex, g_q, nullptr, 0);
+    if (g_gHinv) {
+        dsim_mass_invert(c, ex);
+        ex.run([&](int lane) {
+            for (int it = lane; it < nd * nd; it += Exec::NL) {
+                const int k = it / nd, j = it - nd * k;
+                float acc = 0.f;
+                for (int l = 0; l < nd; ++l) acc += g_gHinv[k * nd + l] * WF(hinv)[j * nd + l];
+                WF(aH)[it] = acc;
+            }
+        });
+        constexpr int HOLD = 8;   // items per lane and block (24, all of Exec::io: the generic adjoint at 275 VGPRs, with scratch)
+        static_assert(HOLD <= DSIM_IO_MAX, "the block's results wait in the early-load registers");
+        const int per = Exec::NL * HOLD / nd, cb = per < nd ? per : nd;   // columns per block (nd <= 64 <= NL: cb >= HOLD)
+        for (int j0 = 0; j0 < nd; j0 += cb) {
+            const int w = nd - j0 < cb ? nd - j0 : cb;
+            ex.run([&](int lane) {
+                float* r = ex.io(lane);
+#pragma unroll
+                for (int p = 0; p < HOLD; ++p) {
+                    const int it = lane + Exec::NL * p;
+                    float acc = 0.f;
+                    if (it < nd * w) {
+                        const int i = it / w, j = j0 + (it - w * i);
+                        for (int k = 0; k < nd; ++k) acc -= WF(hinv)[k * nd + i] * WF(aH)[k * nd + j];
+                        if (g_gH) acc += g_gH[i * nd + j];
+                    }
+                    r[p] = acc;
+                }
+            });
+            ex.run([&](int lane) {
+                const float* r = ex.io(lane);
+#pragma unroll
+                for (int p = 0; p < HOLD; ++p) {
+                    const int it = lane + Exec::NL * p;
+                    if (it < nd * w) {
+                        const int i = it / w;
+                        WF(aH)[i * nd + j0 + (it - w * i)] = r[p];
+                    }
+                }
+            });
+        }
+    } else {
+        ex.run([&](int lane) {
+            for (int it = lane; it < nd * nd; it += Exec::NL) WF(aH)[it] = g_gH ? g_gH[it] : 0.f;
+        });
+    }
+    if (g_gS) {
+        ex.run([&](int lane) {
+            for (int it = lane; it < 6 * nd; it += Exec::NL) WF(aS)[it] = g_gS[it];
+        });
+    }
+    dsim_bwd_mass(c, ex);
+    if constexpr (DsimRowTree<Ctx, Exec>::value) dsim_bwd_bodies_rowtree(c, ex, true);
+    else dsim_bwd_bodies(c, ex, true);
+    ex.run([&](int lane) {
+        for (int k = lane; k < c.d.nq; k += Exec::NL) g_gq[k] = WF(aq)[k];
     });
 }

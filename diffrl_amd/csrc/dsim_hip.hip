@@ -1002,6 +1002,37 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_ground_con_bwd_kernel(KComm
 }
 
 
+// Differentiable mass matrix read-out (dsim_core.hpp: dsim_mass_forward / dsim_mass_backward): one environment per workgroup,
+// plain launch mode.  The forward kernel needs the forward image only; the adjoint re-runs the forward phases and goes on with
+// the mass-matrix and body-level phases of the step adjoint on the adjoint image.
+template <class O, class D, int NW>
+__global__ __launch_bounds__(DSIM_NL * NW) void dsim_mass_kernel(KCommonT<O, D> k, const float* __restrict__ q, float* H,
+                                                               float* Hinv, float* S) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, 6, dsim_const_words<O>(), false> ex;
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex);
+    const size_t nq = k.d.nq, nd = k.d.nd;
+    dsim_mass_forward(c, ex, q + e * nq, H ? H + e * nd * nd : nullptr, Hinv ? Hinv + e * nd * nd : nullptr,
+                      S ? S + e * 6 * nd : nullptr, k.status, e);
+}
+
+template <class O, class D, int NW>
+__global__ __launch_bounds__(DSIM_NL * NW) void dsim_mass_bwd_kernel(KCommonT<O, D> k, const float* __restrict__ q,
+                                                                   const float* __restrict__ gH, const float* __restrict__ gHinv,
+                                                                   const float* __restrict__ gS, float* gq) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, 6, dsim_const_words<O>(), false> ex;
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    const size_t nq = k.d.nq, nd = k.d.nd;
+    dsim_mass_backward(c, ex, q + e * nq, gH ? gH + e * nd * nd : nullptr, gHinv ? gHinv + e * nd * nd : nullptr,
+                       gS ? gS + e * 6 * nd : nullptr, gq + e * nq);
+}
+
+
 thread_local std::string g_err;
 
 int fail(int code, const std::string& msg) {
@@ -1244,6 +1275,8 @@ DSIM_READOUT_FAMILY(dsim_joint_dyn_kernel, true, true)
 DSIM_READOUT_FAMILY(dsim_joint_dyn_bwd_kernel, false, false)
 DSIM_READOUT_FAMILY(dsim_ground_con_kernel, true, true)
 DSIM_READOUT_FAMILY(dsim_ground_con_bwd_kernel, false, false)
+DSIM_READOUT_FAMILY(dsim_mass_kernel, true, true)
+DSIM_READOUT_FAMILY(dsim_mass_bwd_kernel, false, false)
 #undef DSIM_READOUT_FAMILY
 // dsim_body_transforms: the kinematic read-out without qd and v_s, and without the precondition
 struct dsim_body_xf_family : dsim_body_kin_kernel_family {
@@ -1253,7 +1286,8 @@ struct dsim_body_xf_family : dsim_body_kin_kernel_family {
 // on it (or derived from one that is), so a kernel cannot be launched without being opted in to its LDS size.
 using dsim_readout_families = std::tuple<dsim_env_obs_kernel_family, dsim_body_kin_kernel_family, dsim_body_kin_bwd_kernel_family,
                                          dsim_joint_dyn_kernel_family, dsim_joint_dyn_bwd_kernel_family,
-                                         dsim_ground_con_kernel_family, dsim_ground_con_bwd_kernel_family>;
+                                         dsim_ground_con_kernel_family, dsim_ground_con_bwd_kernel_family,
+                                         dsim_mass_kernel_family, dsim_mass_bwd_kernel_family>;
 template <class Fam, class... Listed> constexpr bool dsim_readout_listed(std::tuple<Listed...>*) {
     return (std::is_base_of<Listed, Fam>::value || ...);
 }
@@ -1690,6 +1724,22 @@ int dsim_ground_contacts_backward(const dsim_model* m, int n_envs, const float* 
     if (!q || !qd || !gq || !gqd) return fail(DSIM_ERR_INVALID, "null pointer");
     return launch_readout<dsim_ground_con_bwd_kernel_family>(m, n_envs, hip_stream, q, qd, gpoint, gvel, gforce, glink_wrench, gq,
                                                              gqd);
+}
+
+int dsim_mass_matrix(const dsim_model* m, int n_envs, const float* q, float* H, float* Hinv, float* S, void* hip_stream) {
+    int rc = check_common(m, n_envs, 1.0f, 1, 1);
+    if (rc) return rc;
+    if (!q) return fail(DSIM_ERR_INVALID, "null pointer");
+    if (!H && !Hinv && !S) return fail(DSIM_ERR_INVALID, "no output: H, Hinv and S are all null");
+    return launch_readout<dsim_mass_kernel_family>(m, n_envs, hip_stream, q, H, Hinv, S);
+}
+
+int dsim_mass_matrix_backward(const dsim_model* m, int n_envs, const float* q, const float* gH, const float* gHinv, const float* gS,
+                              float* gq, void* hip_stream) {
+    int rc = check_common(m, n_envs, 1.0f, 1, 1);
+    if (rc) return rc;
+    if (!q || !gq) return fail(DSIM_ERR_INVALID, "null pointer");
+    return launch_readout<dsim_mass_bwd_kernel_family>(m, n_envs, hip_stream, q, gH, gHinv, gS, gq);
 }
 
 /* 0 = generic kernels, >0 = index of the specialised variant in use (diagnostics / tests) */

@@ -490,5 +490,28 @@ class Model:
         fresh host-to-device copy: take it once, outside a graph capture."""
         return torch.as_tensor(np.asarray(self.template().contact_body, dtype=np.int64), device=self.device)
 
+    def mass_matrix(self, state):
+        """(H [articulation_count, nd, nd], Hinv [articulation_count, nd, nd], joint_S_s [joint_dof_count, 6]) of state.joint_q,
+        nd = dofs per articulation, DIFFERENTIABLE in it (Engine.mass_matrix): the joint-space inertia J^T M J + diag(armature)
+        that the step inverts (the reference's model.H is without the armature), its inverse as the step uses it, and the
+        world-frame motion axis of every dof (the reference's State.joint_S_s).  Kinetic energy 0.5 qd^T H qd, inverse dynamics
+        H qdd_des - bias, link Jacobians (link_dof_mask) and task-space inertias back-propagate into the joint state and, through
+        the step that produced it, into the actions; capturable like the steps."""
+        return self.engine().mass_matrix(state.joint_q)
+
+    @property
+    def link_dof_mask(self):
+        """[links_per_articulation, nd] bool: true where dof d belongs to link i or one of its ancestors, so that the Jacobian of
+        link i of one articulation is J_i = (mask[i, :, None] * S).T [6, nd] with S that articulation's [nd, 6] rows of
+        mass_matrix()'s joint_S_s.  A fresh host-to-device copy: take it once, outside a graph capture."""
+        t = self.template()
+        mask = np.zeros((t.n_links, t.n_qd), dtype=bool)
+        for i in range(t.n_links):
+            p = int(t.joint_parent[i])
+            if p >= 0:
+                mask[i] = mask[p]
+            mask[i, int(t.joint_qd_start[i]):int(t.joint_qd_start[i + 1])] = True
+        return torch.as_tensor(mask, device=self.device)
+
     def flatten(self):
         return [v for v in self.__dict__.values() if torch.is_tensor(v)]

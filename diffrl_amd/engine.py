@@ -265,6 +265,34 @@ class Engine:
         words = int(self._lib.dsim_ckpt_floats_mm(self._h, substeps, mm_freq))
         return self._new(n, words)
 
+    def mass_matrix(self, q):
+        """(H [n_envs, n_qd, n_qd], Hinv [n_envs, n_qd, n_qd], S [n_envs * n_qd, 6]): the joint-space inertia J^T M J + diag(armature)
+        that a refresh substep of q inverts (the reference's model.H is without the armature), its Gauss-Jordan inverse with the
+        bits the step and joint_dynamics use, and the world-frame motion axis of every dof (State.joint_S_s) -- of the q HANDED IN,
+        differentiable in it (MassMatrix below; one launch forward, one backward, which asks only for what has a cotangent)."""
+        return MassMatrix.apply(self, q)
+
+    def mass_matrix_forward(self, q):
+        """dsim_mass_matrix on a detached contiguous tensor"""
+        self._check(q, self.n_q, "joint_q")
+        n, nd = q.numel() // self.n_q, self.n_qd
+        H, Hinv, S = self._new(n, nd, nd), self._new(n, nd, nd), self._new(n * nd, 6)
+        self._call(self._lib.dsim_mass_matrix, self._h, n, _ptr(q), _ptr(H), _ptr(Hinv), _ptr(S))
+        return H, Hinv, S
+
+    def mass_matrix_backward(self, q, gH, gHinv, gS):
+        """dsim_mass_matrix_backward: any cotangent may be None (= zeros, no buffer); -> gq, flat"""
+        self._check(q, self.n_q, "joint_q")
+        n, nd = q.numel() // self.n_q, self.n_qd
+        for g, size, name in ((gH, n * nd * nd, "gH"), (gHinv, n * nd * nd, "gHinv"), (gS, n * nd * 6, "gS")):
+            if g is not None:
+                self._check(g, 1, name)
+                if g.numel() != size:
+                    raise capi.DsimError("%s has the wrong size" % name)
+        gq = self._new(n * self.n_q)
+        self._call(self._lib.dsim_mass_matrix_backward, self._h, n, _ptr(q), _ptr(gH), _ptr(gHinv), _ptr(gS), _ptr(gq))
+        return gq
+
     def _check(self, t, cols, name):
         if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
             raise capi.DsimError("%s must be a contiguous float32 tensor on %s" % (name, self.device))
@@ -572,6 +600,30 @@ class GroundContacts(torch.autograd.Function):
         c = lambda g: g.contiguous() if g is not None and g.numel() else None  # noqa: E731
         gq, gqd = ctx.engine.ground_contacts_backward(q, qd, c(gpoint), c(gvel), c(gforce), c(glw))
         return None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1])
+
+
+class MassMatrix(torch.autograd.Function):
+    """joint_q -> (H, Hinv, S): the mass matrix read-out of a state with its adjoint (dsim_mass_matrix /
+    dsim_mass_matrix_backward); the backward launch re-runs the forward pass on the saved input.  The quaternion blocks of the
+    returned joint_q gradient have no component along the quaternion, as SimStep's."""
+
+    @staticmethod
+    def forward(ctx, engine, q):
+        qc = q.detach().contiguous()
+        out = engine.mass_matrix_forward(qc)
+        ctx.engine = engine
+        ctx.shape = q.shape
+        ctx.set_materialize_grads(False)   # an output the loss does not read costs no cotangent buffer
+        ctx.save_for_backward(qc)
+        return out
+
+    @staticmethod
+    def backward(ctx, gH, gHinv, gS):
+        if gH is None and gHinv is None and gS is None:
+            return None, None
+        q, = ctx.saved_tensors
+        c = lambda g: g.contiguous() if g is not None else None  # noqa: E731
+        return None, ctx.engine.mass_matrix_backward(q, c(gH), c(gHinv), c(gS)).view(ctx.shape)
 
 
 class SimStep(torch.autograd.Function):

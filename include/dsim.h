@@ -312,6 +312,31 @@ int dsim_ground_contacts_backward(const dsim_model* m, int n_envs, const float* 
                                   const float* glink_wrench /* each may be NULL = zeros */,
                                   float* gq, float* gqd, void* hip_stream);
 
+/* Differentiable mass matrix: the joint-space inertia of a given q, its inverse and the joint motion axes, and the reverse pass.
+ *   H [N][nd][nd]     the matrix the step inverts at a refresh substep of q: J^T M J (composite-rigid-body form) PLUS the joint
+ *                     armature on the diagonal.  The reference's model.H is WITHOUT the armature (it adds it inside its
+ *                     factorisation): model.H = H - diag(joint_armature);
+ *   Hinv [N][nd][nd]  the Gauss-Jordan inverse of H exactly as the step kernels compute it: the same bits as the inverse a refresh
+ *                     substep and dsim_joint_dynamics use for this q;
+ *   S [N][nd][6]      the world-frame motion axis (angular, linear about the world origin) of every dof, the reference's
+ *                     State.joint_S_s; the identity rows of a free joint are written too.  The Jacobian of link i is made of the
+ *                     rows S_d of the dofs d of link i and its ancestors.
+ * There is no qd and no step length: nothing here depends on them.  Each output may be NULL (skipped; without Hinv the inversion
+ * is skipped as well), not all three.
+ * The backward call maps cotangents on the three tensors (each may be NULL = zeros; gH and gHinv need not be symmetric) to the
+ * cotangent on q, which is WRITTEN, not accumulated.  It re-runs the forward pass on q: nothing is kept between the two calls.
+ * adj H = gH - Hinv^T gHinv Hinv^T with the kernel's own fp32 inverse, adj S = gS, then the mass-matrix and body levels of the
+ * step adjoint.  Pose cotangents are world-frame wrenches: the quaternion blocks of gq have NO component
+ * along the quaternion -- project the reference's literal gradient onto the tangent space before comparing.
+ * Like every call here: device pointers borrowed for the call, launches on the caller's stream, no host synchronisation,
+ * deterministic (no atomics).  Precondition: unit quaternions in q; the forward call checks it like the step functions do (the
+ * NEXT call on the model returns DSIM_ERR_INVALID), the backward call does not check again. */
+int dsim_mass_matrix(const dsim_model* m, int n_envs, const float* q,
+                     float* H, float* Hinv, float* S /* each may be NULL, not all three */, void* hip_stream);
+int dsim_mass_matrix_backward(const dsim_model* m, int n_envs, const float* q,
+                              const float* gH, const float* gHinv, const float* gS /* each may be NULL = zeros */,
+                              float* gq, void* hip_stream);
+
 /* ---- fused environment surface -------------------------------------
  * The per-step torch glue of the reference environments -- action clip + scale into joint_act /
  * muscle activations (envs/ant.py:157-163, humanoid.py:188-211, snu_humanoid.py:245-271,
