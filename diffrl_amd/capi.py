@@ -144,8 +144,12 @@ ABI = {
     "dsim_mass_matrix_backward": (_int, [_vp, _int] + [_vp] * 6),
     "dsim_step_backward_multi": (_int, [_vp, _int, _int, _int] + [_vp] * 3 + _step + [_vp] * 7),
     "dsim_step_jacobian": (_int, [_vp, _int] + [_vp] * 3 + _step + [_vp] * 4),
+    "dsim_model_set_params": (_int, [_vp, _int, _vp, _vp]),
+    "dsim_step_backward_params": (_int, [_vp, _int] + [_vp] * 3 + _step + [_vp] * 9),
 }
 EXPORTS = tuple(ABI)
+# DSIM_PARAM_* of include/dsim.h, in the order Engine.set_params walks the fields of a StepParameters
+PARAM_TARGET_KE, PARAM_TARGET_KD, PARAM_LIMIT_KE, PARAM_LIMIT_KD, PARAM_TARGET, PARAM_CONTACT_MATERIAL = range(6)
 del _vp, _int, _f, _spec, _step
 
 _libs = {}

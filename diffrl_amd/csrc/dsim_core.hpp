@@ -61,6 +61,44 @@ template <class O, class D, bool LEAN_ = false> struct DsimCtxT {
     float h;   // substep length
 };
 typedef DsimCtxT<DsimOff, DsimDims> DsimCtx;
+// Model-parameter gradients (dsim_step_backward_params): the context of dsim_bwd_param_kernel.  The step adjoint tests
+// DsimParamGrad<Ctx> with `if constexpr` where it holds the cotangent of a dof's tau or of a contact's force, and adds that
+// item's parameter terms to accumulators that live BEHIND the adjoint image (`pg`: [5 nd] per dof -- target_ke, target_kd, target,
+// limit_ke, limit_kd -- then [4 C] per contact -- ke, kd, kf, mu).  A word is only ever touched by the lane that owns its dof or
+// contact in that phase (the ownership loops are the same in every substep): no atomics, sums in substep order.  With any other
+// context the branches do not exist.
+template <class O, class D, bool LEAN_ = false> struct DsimParCtxT : DsimCtxT<O, D, LEAN_> {
+    static constexpr bool PARAM_GRAD = true;
+    float* pg;         // LDS accumulators, dsim_par_words(nd, C) words
+    float* g_dof;      // this environment's [5][nd] output, or null
+    float* g_contact;  // this environment's [C][4] output, or null
+};
+template <class Ctx, class = void> struct DsimParamGrad : std::false_type {};
+template <class Ctx> struct DsimParamGrad<Ctx, std::void_t<decltype(Ctx::PARAM_GRAD)>> : std::true_type {};
+DSIM_FN int dsim_par_words(int nd, int C) { return 5 * nd + 4 * C; }
+// one dof's terms (jcalc_tau, sim.py:1452-1489): `at` the cotangent of its tau, q / qd / target / limits of its coordinate
+// (a ball joint: q = its vector component k, no target or limit terms); free and fixed joints have none
+template <class Ctx>
+DSIM_FN void dsim_par_dof(const Ctx& c, int d, bool hinge, bool ball, float q, float qd, float target, float lower, float upper,
+                          float tke, float at) {
+    if constexpr (DsimParamGrad<Ctx>::value) {
+        float* p = c.pg + 5 * d;
+        if (hinge) {
+            float lim = 0.0f;   // the branch the forward pass took (dsim_tau_lane), as evaluated
+            if (q < lower) lim = lower - q;
+            if (q > upper) lim = upper - q;
+            const float mqd = (0.0f - qd) * at;
+            p[0] += (target - q) * at;
+            p[1] += mqd;
+            p[2] += tke * at;
+            p[3] += lim * at;
+            p[4] += mqd;        // the limit damping acts whether or not a limit is exceeded
+        } else if (ball) {
+            p[0] += (0.0f - q) * at;
+            p[1] += (0.0f - qd) * at;
+        }
+    }
+}
 // words of one substep's checkpoint row: the saved block (everything the adjoint reads) or, in the lean mode, only (q, qd)
 template <class Ctx> DSIM_FN int dsim_row(const Ctx& c) { return Ctx::LEAN ? c.o.xsc - c.o.q : c.o.save_words; }
 
@@ -3189,6 +3227,8 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_wave(const Ctx& c, 
                 WF(aq)[qi] = g_q + dq * at;
                 WF(aqd)[lane] = g + (-tkd - lkd) * at;
                 WF(aact)[lane] = g_act + at;
+                if constexpr (DsimParamGrad<Ctx>::value)
+                    dsim_par_dof(c, lane, true, false, q, WF(qd)[lane], CF(target)[qi], lower, upper, tke, at);
             } else {
                 WF(aqd)[lane] = g;   // (free root: tau has no joint-space terms)
             }
@@ -3319,6 +3359,8 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_space(const Ctx& c,
                 WF(aq)[qi] = g_q + (-tke) * at;
                 WF(aqd)[d] = g_qd + (-tkd) * at;
             }
+            if constexpr (DsimParamGrad<Ctx>::value)
+                dsim_par_dof(c, d, hinge, ball, q, WF(qd)[d], CF(target)[qi], lower, upper, tke, at);
         }
     };
     // (main) the mass-matrix cotangent accumulators (registers of the main wave) and the per-dof block, (side) af
@@ -3515,6 +3557,22 @@ template <int NLX, class Ctx, class Exec> DSIM_FN void dsim_bwd_external_items_n
             a_p += cross(a_dp, vb.w);
             wr = mksv(cross(x, a_p), a_p);
             tw = mksv(cross(p, a_dp), a_dp);
+            if constexpr (DsimParamGrad<Ctx>::value) {
+                // cotangents of this contact's (ke, kd, kf, mu): fn = cc ke, fd = vmin kd (0 - cc), smin = kf lt | -mu cc ke
+                float* pc = c.pg + 5 * c.d.nd + 4 * k;
+                const float cas = cc * a_s;
+                float a_ke = cc * a_fnfd, a_kf = 0.f, a_mu = 0.f;
+                if (first) {
+                    a_kf = lt * a_s;
+                } else {
+                    a_ke -= mu * cas;
+                    a_mu = 0.0f - cas * ke;
+                }
+                pc[0] += a_ke;
+                pc[1] += (vmin * (0.0f - cc)) * a_fnfd;
+                pc[2] += a_kf;
+                pc[3] += a_mu;
+            }
         }
         float* o = WF(acx) + 12 * k;
         stsv(o, wr);
@@ -4341,6 +4399,8 @@ DSIM_FN void dsim_sim_step_backward(const Ctx& c, Exec& ex, int substeps, int mm
             WF(mact)[k] = g_mact[k];
             WF(amact)[k] = 0.f;
         }
+        if constexpr (DsimParamGrad<Ctx>::value)
+            for (int k = lane; k < dsim_par_words(nd, c.d.C); k += Exec::NL) c.pg[k] = 0.f;
     });
     const int groups = (substeps + mm_freq - 1) / mm_freq;
     for (int g = groups - 1; g >= 0; --g) {
@@ -4416,6 +4476,16 @@ DSIM_FN void dsim_sim_step_backward(const Ctx& c, Exec& ex, int substeps, int mm
         }
         if (g_gmact)
             for (int k = lane; k < M; k += Exec::NL) g_gmact[k] = WF(amact)[k];
+        if constexpr (DsimParamGrad<Ctx>::value) {
+            // per dof [5][nd] and per contact [C][4], summed over the substeps; written, every word by one lane
+            if (c.g_dof)
+                for (int it = lane; it < 5 * nd; it += Exec::NL) {
+                    const int j = it / nd, d = it - nd * j;
+                    c.g_dof[it] = c.pg[5 * d + j];
+                }
+            if (c.g_contact)
+                for (int k = lane; k < 4 * c.d.C; k += Exec::NL) c.g_contact[k] = c.pg[5 * nd + k];
+        }
     });
 }
 

@@ -814,6 +814,31 @@ __global__ __launch_bounds__((DSIM_NL * NW), DSIM_WIDE_WAVES(NW)) void dsim_bwd_
                            s.gmact);
 }
 
+// dsim_step_backward_params: the step adjoint of dsim_bwd_kernel (plain launch mode: the same bits) on the context that switches the
+// parameter accumulations on (dsim_core.hpp: DsimParCtxT).  The accumulators are the dsim_par_words(nd, C) LDS words behind the
+// adjoint image, which only these kernels are launched with; every output word is written by one lane, environments are not summed.
+struct DsimParArgs {
+    const float *ckpt, *act, *mact, *gq_out, *gqd_out;
+    float *gq_in, *gqd_in, *gact, *gmact;
+    float *g_dof, *g_contact;   // [n_envs][5][nd], [n_envs][C][4]; either may be null
+};
+template <class O, class D, int NW, bool LEAN>
+__global__ __launch_bounds__((DSIM_NL * NW), DSIM_WIDE_WAVES(NW)) void dsim_bwd_param_kernel(KCommonT<O, D> k, DsimParArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = (int)blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, dsim_pf_regs<O, NW, LEAN, DSIM_MODE_PLAIN>(), dsim_const_words<O>(), false, 1> ex;
+    DsimParCtxT<O, D, LEAN> c;
+    static_cast<DsimCtxT<O, D, LEAN>&>(c) = start_env<LEAN, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    const size_t nq = k.d.nq, nd = k.d.nd, M = k.d.M, C = k.d.C;
+    c.pg = lds + k.o.total_words;
+    c.g_dof = a.g_dof ? a.g_dof + e * 5 * nd : nullptr;
+    c.g_contact = (a.g_contact && C) ? a.g_contact + e * 4 * C : nullptr;
+    dsim_sim_step_backward(c, ex, k.substeps, k.mm_freq, a.ckpt + (size_t)e * k.ckpt_stride, a.act + e * nd,
+                           M ? a.mact + e * M : nullptr, a.gq_out + e * nq, a.gqd_out + e * nd, a.gq_in + e * nq,
+                           a.gqd_in + e * nd, a.gact ? a.gact + e * nd : nullptr, (a.gmact && M) ? a.gmact + e * M : nullptr);
+}
+
 // dsim_step_backward_literal, second launch: gq_in[quaternion block of joint j] += rho_j q_j (dsim_literal.hpp).  One thread per
 // (environment, link); threads of links without a quaternion joint leave at once.  Run-time layout for every model.
 // row_words: floats of one substep's checkpoint row in the model's checkpoint mode (both modes start a row with q, qd).
@@ -1292,12 +1317,14 @@ template <class Fam, class... Listed> constexpr bool dsim_readout_listed(std::tu
     return (std::is_base_of<Listed, Fam>::value || ...);
 }
 
-// f(kernel) for every kernel of a model outside the step families: the read-outs above and the multi-cotangent sweep (full and
-// lean checkpoints; step_backward_multi launches it).
+// f(kernel) for every kernel of a model outside the step families: the read-outs above, the multi-cotangent sweep and the
+// parameter-gradient sweep (full and lean checkpoints; step_backward_multi and dsim_step_backward_params launch them).
 template <class O, class D, int NW, class F, class... Listed> void for_each_readout_kernel(F&& f, std::tuple<Listed...>*) {
     (f(reinterpret_cast<const void*>(Listed::template kernel<O, D, NW>())), ...);
     f(reinterpret_cast<const void*>(&dsim_bwd_multi_kernel<O, D, NW, false>));
     f(reinterpret_cast<const void*>(&dsim_bwd_multi_kernel<O, D, NW, true>));
+    f(reinterpret_cast<const void*>(&dsim_bwd_param_kernel<O, D, NW, false>));
+    f(reinterpret_cast<const void*>(&dsim_bwd_param_kernel<O, D, NW, true>));
 }
 template <class O, class D, int NW, class F> void for_each_readout_kernel(F&& f) {
     for_each_readout_kernel<O, D, NW>(f, static_cast<dsim_readout_families*>(nullptr));
@@ -1587,6 +1614,53 @@ int dsim_step_jacobian(const dsim_model* m, int n_envs, const float* ckpt, const
     a.gq_in = J_state; a.gqd_in = J_state + nq; a.gact = J_act; a.gmact = J_muscle;              // [gq_in | gqd_in] = row k of J_state
     a.gq_in_stride = K; a.gqd_in_stride = K; a.gact_stride = nd; a.gmact_stride = M;
     return step_backward_multi(m, n_envs, dt, substeps, mm_freq, a, hip_stream);
+}
+
+int dsim_model_set_params(dsim_model* m, int field, const float* dev_values, void* hip_stream) {
+    if (!m) return fail(DSIM_ERR_INVALID, "null model");
+    if (!dev_values) return fail(DSIM_ERR_INVALID, "null pointer (dev_values)");
+    const DsimOff& o = m->lay.o;
+    const DsimDims& d = m->lay.d;
+    int off = 0, n = 0;
+    switch (field) {
+    case DSIM_PARAM_TARGET_KE: off = o.tke; n = d.L; break;
+    case DSIM_PARAM_TARGET_KD: off = o.tkd; n = d.L; break;
+    case DSIM_PARAM_LIMIT_KE: off = o.lke; n = d.L; break;
+    case DSIM_PARAM_LIMIT_KD: off = o.lkd; n = d.L; break;
+    case DSIM_PARAM_TARGET: off = o.target; n = d.nq; break;
+    case DSIM_PARAM_CONTACT_MATERIAL: off = o.cmat; n = 4 * d.C; break;
+    default: return fail(DSIM_ERR_INVALID, "unknown parameter field " + std::to_string(field));
+    }
+    if (int rc = check_device(m)) return rc;
+    if (n == 0) return DSIM_OK;   // (contact materials of a model without contacts)
+    // the six arrays are plain copies in the constant block (dsim_layout.hpp: put_f); nothing on the host is derived from them
+    hipError_t e = hipMemcpyAsync(m->d_cblob + off, dev_values, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice,
+                                  static_cast<hipStream_t>(hip_stream));
+    if (e != hipSuccess) return hip_fail(e, "dsim_model_set_params");
+    return DSIM_OK;
+}
+
+int dsim_step_backward_params(const dsim_model* m, int n_envs, const float* ckpt, const float* act, const float* muscle_act,
+                              float dt, int substeps, int mm_freq, const float* gq_out, const float* gqd_out, float* gq_in,
+                              float* gqd_in, float* gact, float* gmuscle_act, float* g_dof, float* g_contact, void* hip_stream) {
+    int rc = check_common(m, n_envs, dt, substeps, mm_freq);
+    if (rc) return rc;
+    if (!ckpt || !act || !gq_out || !gqd_out || !gq_in || !gqd_in) return fail(DSIM_ERR_INVALID, "null pointer (ckpt/act/grad)");
+    if (m->lay.d.M > 0 && !muscle_act) return fail(DSIM_ERR_INVALID, "model has muscles but muscle_act is null");
+    if (!g_dof && !g_contact) return fail(DSIM_ERR_INVALID, "g_dof and g_contact are both null (dsim_step_backward is that call)");
+    const size_t bytes = ((size_t)m->lay.o.total_words + (size_t)(5 * m->lay.d.nd + 4 * m->lay.d.C)) * 4;   // + dsim_par_words(nd, C)
+    if (bytes > 160 * 1024) return fail(DSIM_ERR_LIMIT, "model needs more than 160 KiB of LDS per environment with the parameter accumulators");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return dispatch(m, [&](auto o, auto d, auto nw) {
+        using O = decltype(o);
+        using D = decltype(d);
+        constexpr int NW = decltype(nw)::value;
+        auto k = make_k(m, o, d, n_envs, dt, substeps, mm_freq);
+        const DsimParArgs a{ckpt, act, muscle_act, gq_out, gqd_out, gq_in, gqd_in, gact, gmuscle_act, g_dof, g_contact};
+        if (m->lean) hipLaunchKernelGGL((dsim_bwd_param_kernel<O, D, NW, true>), dim3(n_envs), dim3(DSIM_NL * NW), bytes, st, k, a);
+        else hipLaunchKernelGGL((dsim_bwd_param_kernel<O, D, NW, false>), dim3(n_envs), dim3(DSIM_NL * NW), bytes, st, k, a);
+        return launched("launch dsim_bwd_param_kernel");
+    });
 }
 
 int64_t dsim_literal_scratch_floats(const dsim_model* m) {

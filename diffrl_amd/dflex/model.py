@@ -513,5 +513,20 @@ class Model:
             mask[i, int(t.joint_qd_start[i]):int(t.joint_qd_start[i + 1])] = True
         return torch.as_tensor(mask, device=self.device)
 
+    def step_parameters(self):
+        """The parameters a step is differentiable in, as device tensors cloned from the template and shared by all articulations
+        (engine.StepParameters): joint_target_ke / joint_target_kd / joint_limit_ke / joint_limit_kd [links_per_articulation],
+        joint_target [coords_per_articulation], contact_material [contacts_per_articulation, 4] = (ke, kd, kf, mu) per contact
+        slot.  Set requires_grad on the ones to fit and hand the object to SemiImplicitIntegrator.forward(..., params=p); tie the
+        contacts of one shape together with contact_shape.  Fresh host-to-device copies: take it once, outside a graph capture."""
+        return self.engine().step_parameters()
+
+    @property
+    def contact_shape(self):
+        """[contacts_per_articulation] int64: the shape (within its articulation) that each contact slot belongs to -- a shape's
+        material in the slots' terms is contact_material[contact_shape == s].  A fresh host-to-device copy."""
+        mat = self._contacts[3] if (self.ground and self._contacts is not None) else []
+        return torch.as_tensor(np.asarray(mat, dtype=np.int64), device=self.device)
+
     def flatten(self):
         return [v for v in self.__dict__.values() if torch.is_tensor(v)]

@@ -15,6 +15,21 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
+class StepParameters:
+    """The model parameters the step is differentiable in, as device tensors shared by all environments: joint_target_ke,
+    joint_target_kd, joint_limit_ke, joint_limit_kd [n_links], joint_target [n_q], contact_material [C, 4] (ke, kd, kf, mu per
+    contact slot).  Engine.step_parameters() clones them from the template; set requires_grad on the ones to fit."""
+    FIELDS = ("joint_target_ke", "joint_target_kd", "joint_limit_ke", "joint_limit_kd", "joint_target", "contact_material")
+
+    def __init__(self, **tensors):
+        for k in self.FIELDS:
+            setattr(self, k, tensors[k])
+
+    def tensors(self):
+        """in the order of DSIM_PARAM_* (include/dsim.h)"""
+        return tuple(getattr(self, k) for k in self.FIELDS)
+
+
 class Engine:
     """Owns the device copy of one articulation template on one GPU."""
 
@@ -395,6 +410,92 @@ class Engine:
                    substeps, mm_freq, _ptr(J), _ptr(Ja), _ptr(Jm))
         return J, Ja, Jm
 
+    # ---- model parameters of the step ------------------------------------------------------------------
+    def step_parameters(self):
+        """StepParameters cloned from the template (fresh host-to-device copies: take them once, outside a graph capture)"""
+        t = self.template
+        dev = lambda a, *shape: torch.as_tensor(a, dtype=torch.float32).reshape(*shape).to(self.device)  # noqa: E731
+        return StepParameters(joint_target_ke=dev(t.joint_target_ke, -1), joint_target_kd=dev(t.joint_target_kd, -1),
+                              joint_limit_ke=dev(t.joint_limit_ke, -1), joint_limit_kd=dev(t.joint_limit_kd, -1),
+                              joint_target=dev(t.joint_target, -1), contact_material=dev(t.contact_material, -1, 4))
+
+    def set_params(self, p):
+        """dsim_model_set_params for every field of p (a StepParameters, or its six tensors in that order; an entry may be None =
+        left as it is): device-to-device copies on the current stream, capturable, no host synchronisation.  Every later launch
+        on this model ordered after them -- step, fused env step, read-outs -- runs under these values, for ALL environments; the
+        model keeps what was last set until reset_params()."""
+        ts = p.tensors() if isinstance(p, StepParameters) else tuple(p)
+        t = self.template
+        sizes = (t.n_links,) * 4 + (t.n_q, 4 * t.n_contacts)
+        if len(ts) != 6:
+            raise capi.DsimError("set_params takes the six tensors of a StepParameters")
+        for field, (x, size) in enumerate(zip(ts, sizes)):
+            if x is None:
+                continue
+            x = x.detach()
+            self._check(x, 1, StepParameters.FIELDS[field])
+            if x.numel() != size:
+                raise capi.DsimError("%s has %d elements, the model has %d" % (StepParameters.FIELDS[field], x.numel(), size))
+            if size:
+                self._call(self._lib.dsim_model_set_params, self._h, field, _ptr(x))
+
+    def reset_params(self):
+        """back to the template's values"""
+        if getattr(self, "_params0", None) is None:
+            self._params0 = self.step_parameters()
+        self.set_params(self._params0)
+
+    def _fold_index(self):
+        """(link of every dof [nd], the hinge / slider dofs [k], their coordinates [k]) on the device"""
+        if getattr(self, "_fold", None) is None:
+            t = self.template
+            link, dofs, coords = [], [], []
+            for i in range(t.n_links):
+                d0, d1 = int(t.joint_qd_start[i]), int(t.joint_qd_start[i + 1])
+                link += [i] * (d1 - d0)
+                if int(t.joint_type[i]) in (0, 1):   # prismatic, revolute: the dof's coordinate carries the target
+                    dofs.append(d0)
+                    coords.append(int(t.joint_q_start[i]))
+            mk = lambda a: torch.as_tensor(a, dtype=torch.int64).to(self.device)  # noqa: E731
+            self._fold = (mk(link), mk(dofs), mk(coords))
+        return self._fold
+
+    def fold_param_grads(self, g_dof, g_contact, need=(True,) * 6):
+        """what backward_params returns per environment and dof / contact slot -> the gradients of the six StepParameters tensors
+        (in their order; None where not needed): summed over the environments, dofs folded into their links (a ball joint's three
+        dofs share one gain) and, for joint_target, into the coordinate of their hinge / slider"""
+        gp = [None] * 6
+        if any(need[:5]):
+            link, dofs, coords = self._fold_index()
+            d = g_dof.sum(dim=0)   # [5, nd]: target_ke, target_kd, target, limit_ke, limit_kd
+            for field, row in ((0, 0), (1, 1), (2, 3), (3, 4)):
+                if need[field]:
+                    gp[field] = torch.zeros(self.template.n_links, device=d.device).index_add_(0, link, d[row])
+            if need[4]:
+                gp[4] = torch.zeros(self.n_q, device=d.device).index_add_(0, coords, d[2][dofs])
+        if need[5]:
+            gp[5] = g_contact.sum(dim=0)
+        return gp
+
+    def backward_params(self, ckpt, act, mact, dt, substeps, mm_freq, gq_out, gqd_out, want_dof=True, want_contact=True):
+        """dsim_step_backward_params -> (gq, gqd, gact, gmuscle_act | None, g_dof [n_envs, 5, n_qd] | None, g_contact
+        [n_envs, C, 4] | None): the state gradients of backward(), bit for bit, and per environment the gradient terms of every
+        dof for (target_ke, target_kd, target, limit_ke, limit_kd) and of every contact slot for (ke, kd, kf, mu), summed over
+        the substeps.  The checkpoint is consumed under the parameter values its forward ran with."""
+        self._check_ckpt(ckpt, substeps, mm_freq)
+        n = ckpt.shape[0]
+        self._check_act(act, mact, n)
+        gq_out, gqd_out = gq_out.contiguous(), gqd_out.contiguous()
+        Cn = self.template.n_contacts
+        gq, gqd, gact = self._new(n * self.n_q), self._new(n * self.n_qd), self._new(n * self.n_qd)
+        gm = self._new(n * self.n_muscles) if self.n_muscles else None
+        g_dof = self._new(n, 5, self.n_qd) if want_dof else None
+        g_con = (self._new(n, Cn, 4) if Cn else torch.zeros(n, 0, 4, device=self.device)) if want_contact else None
+        self._call(self._lib.dsim_step_backward_params, self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact) if self.n_muscles else None,
+                   C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gm),
+                   _ptr(g_dof), _ptr(g_con))
+        return gq, gqd, gact, gm, g_dof, g_con
+
     def _check_act(self, act, mact, n):
         """the actuation a checkpoint of n environments is consumed with"""
         self._check(act, self.n_qd, "joint_act")
@@ -485,6 +586,50 @@ class EpisodeIO:
         ep.noise_qd = self.noise_qd.data_ptr() if self.noise_qd is not None else None
         ep.noise_angle, ep.seed = self.noise_angle, self.seed & 0xFFFFFFFFFFFFFFFF
         return ep, (obs_before, done)
+
+
+class SimStepParams(torch.autograd.Function):
+    """SimStep with the model parameters as inputs: (joint_q, joint_qd, joint_act, muscle_activation, six parameter tensors) ->
+    (joint_q', joint_qd').  forward sets the parameters on the model, then steps; backward sets the SAVED tensors again (another
+    forward with other values may have run in between: the checkpoint is consumed under the values it was written with),
+    launches dsim_step_backward_params, folds dofs into links (joint_target: into coordinates) and sums over the environments.
+    All of it on the current stream, so a captured rollout whose leaves are parameter tensors sees in-place updates at the next
+    replay.  The model keeps what was set last -- after a backward, the values of that backward's forward."""
+
+    @staticmethod
+    def forward(ctx, engine, dt, substeps, mm_freq, q, qd, act, mact, *params):
+        q, qd, act = q.contiguous(), qd.contiguous(), act.contiguous()
+        mact = mact.contiguous() if mact is not None else None
+        params = tuple(p.contiguous() for p in params)
+        need = any(t is not None and t.requires_grad for t in (q, qd, act, mact) + params)
+        engine.set_params(params)
+        q_out, qd_out, ckpt = engine.forward(q.detach(), qd.detach(), act.detach(),
+                                             mact.detach() if mact is not None else None, dt, substeps, mm_freq, need,
+                                             keep_q_in=True)
+        ctx.engine, ctx.dt, ctx.substeps, ctx.mm_freq = engine, dt, substeps, mm_freq
+        ctx.has_mact = mact is not None
+        ctx.shapes = (q.shape, qd.shape, act.shape, mact.shape if mact is not None else None)
+        if need:
+            ctx.save_for_backward(ckpt, act.detach(), mact.detach() if mact is not None else act.new_empty(0), *params)
+        return q_out.view(q.shape), qd_out.view(qd.shape)
+
+    @staticmethod
+    def backward(ctx, gq_out, gqd_out):
+        ckpt, act, mact = ctx.saved_tensors[:3]
+        params = ctx.saved_tensors[3:]
+        e = ctx.engine
+        if gq_out is None:
+            gq_out = torch.zeros(ctx.shapes[0], dtype=torch.float32, device=ckpt.device)
+        if gqd_out is None:
+            gqd_out = torch.zeros(ctx.shapes[1], dtype=torch.float32, device=ckpt.device)
+        need = ctx.needs_input_grad[8:]
+        e.set_params(params)
+        gq, gqd, gact, gm, g_dof, g_con = e.backward_params(ckpt, act, mact if ctx.has_mact else None, ctx.dt, ctx.substeps,
+                                                            ctx.mm_freq, gq_out, gqd_out, want_dof=any(need[:5]) or not need[5],
+                                                            want_contact=need[5])
+        gp = [g.view(p.shape) if g is not None else None for g, p in zip(e.fold_param_grads(g_dof, g_con, need), params)]
+        return (None, None, None, None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), gact.view(ctx.shapes[2]),
+                gm.view(ctx.shapes[3]) if ctx.has_mact else None, *gp)
 
 
 class EnvStep(torch.autograd.Function):

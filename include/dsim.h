@@ -228,6 +228,57 @@ int dsim_step_jacobian(const dsim_model* m, int n_envs,
                        float dt, int substeps, int mm_freq,
                        float* J_state, float* J_act, float* J_muscle, void* hip_stream);
 
+/* Model parameters of the step, on the device (ABI 110: functions added).
+ *
+ * dsim_model_set_params overwrites ONE parameter array of the model's device-side constant block from DEVICE memory: a
+ * device-to-device copy enqueued on hip_stream -- asynchronous, capturable in a HIP graph, no host synchronisation.
+ *   field                          dev_values            (shapes of dsim_model_desc)
+ *   DSIM_PARAM_TARGET_KE           [L]     joint_target_ke
+ *   DSIM_PARAM_TARGET_KD           [L]     joint_target_kd
+ *   DSIM_PARAM_LIMIT_KE            [L]     joint_limit_ke
+ *   DSIM_PARAM_LIMIT_KD            [L]     joint_limit_kd
+ *   DSIM_PARAM_TARGET              [n_q]   joint_target
+ *   DSIM_PARAM_CONTACT_MATERIAL    [C][4]  contact_material (ke, kd, kf, mu per contact slot); C == 0: DSIM_OK, nothing done
+ * ORDERING: the copy is ordered like a kernel of hip_stream.  Every launch on the model that is enqueued on that stream after
+ * the call, or on a stream ordered after it (an event, a graph dependency), reads the new values -- the step kernels in every
+ * launch mode, the fused env kernels, the read-outs, the literal launch; a launch that runs concurrently on an unordered
+ * stream may read either.  The values are shared by all environments of the model and stay until the next call for that field
+ * (nothing on the host is derived from these six arrays, so nothing else is recomputed).  dev_values may be reused once the
+ * copy has run.  NULL dev_values or an unknown field: DSIM_ERR_INVALID. */
+#define DSIM_PARAM_TARGET_KE 0
+#define DSIM_PARAM_TARGET_KD 1
+#define DSIM_PARAM_LIMIT_KE 2
+#define DSIM_PARAM_LIMIT_KD 3
+#define DSIM_PARAM_TARGET 4
+#define DSIM_PARAM_CONTACT_MATERIAL 5
+int dsim_model_set_params(dsim_model* m, int field, const float* dev_values, void* hip_stream);
+
+/* dsim_step_backward with the gradients of those parameters: same arguments, same conventions, and gq_in, gqd_in, gact,
+ * gmuscle_act equal to dsim_step_backward's BIT FOR BIT (the same arithmetic; one kernel family more, plain launch mode).
+ * Two more outputs, both WRITTEN (not accumulated), either may be NULL but not both (DSIM_ERR_INVALID):
+ *   g_dof     [N][5][n_qd]  per environment and dof, that dof's contribution to the gradient of (target_ke, target_kd, target,
+ *                           limit_ke, limit_kd), summed over the substeps.  Kept per DOF: the caller folds dofs into links
+ *                           (joint_qd_start; a ball joint's three dofs share one gain) or, for `target`, into the coordinate
+ *                           of a hinge / slider dof, and sums over the environments -- the kernel sums neither (no atomics,
+ *                           the same bits in every run).  With at the cotangent of the dof's tau in a substep (jcalc_tau,
+ *                           sim.py:1452-1489):
+ *                             revolute / prismatic   -(q - target) at, -qd at, +target_ke at, (lower - q) at or (upper - q) at
+ *                                                    where the forward pass took that limit branch (else 0), -qd at (the limit
+ *                                                    damping is unconditional);
+ *                             ball                   -q[cs + k] at, -qd at, 0, 0, 0;   free / fixed: zeros.
+ *   g_contact [N][C][4]     per environment and contact slot, the gradient of that contact's (ke, kd, kf, mu), summed over the
+ *                           substeps (eval_rigid_contacts_art, sim.py:1137-1206): zeros for a contact that does not penetrate;
+ *                           kf only in the kf |vt| < -mu c ke friction branch, mu only in the other.  Not touched when C == 0.
+ * The checkpoint is consumed in the mode it was written in AND under the parameter values the forward call ran with: set the
+ * same values again (dsim_model_set_params) if they were changed in between.  There is no literal, multi-cotangent or fused-env
+ * variant of this call. */
+int dsim_step_backward_params(const dsim_model* m, int n_envs,
+                              const float* ckpt, const float* act, const float* muscle_act,
+                              float dt, int substeps, int mm_freq,
+                              const float* gq_out, const float* gqd_out,
+                              float* gq_in, float* gqd_in, float* gact, float* gmuscle_act,
+                              float* g_dof, float* g_contact, void* hip_stream);
+
 /* Derived body transforms of a joint state: X_sc[N][L][7] (link frames in the world, what eval_rigid_fk writes to
  * State.body_X_sc, sim.py:1638-1678) and, if X_sm is not NULL, X_sm[N][L][7] = X_sc o X_cm (State.body_X_sm: the bodies'
  * centre-of-mass frames).  The reference's State carries them after every forward() (model.py:338-392; read by
