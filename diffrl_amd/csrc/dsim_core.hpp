@@ -310,6 +310,9 @@ struct DsimTopoRegs {
     int qk_link[DSIM_QUAD_DEPTH], qk_cs[DSIM_QUAD_DEPTH], qk_ds[DSIM_QUAD_DEPTH];
     float qk_w[DSIM_QUAD_DEPTH];
     DsimQuadConsts qc;
+    // quad body level of the adjoint (DsimQuadBodies): link of the lane's quad (0 and qb_on = 0 where the quad holds none), its
+    // joint type (-1: none), first coordinate and first dof
+    int qb_i, qb_on, qb_type, qb_cs, qb_ds;
 };
 
 // Row-tree form of the body-level adjoint (dsim_bwd_bodies_rowtree): specialised kernels of pre-order trees of at most 32 links
@@ -489,6 +492,73 @@ template <class Ctx, int NL> struct DsimQuadKin {
         else return false;
     }();
 };
+// Quad form of the adjoint's body level (dsim_bwd_bodies_rowtree, dsim_math_quad.hpp): four lanes per link, one vector component
+// each, for row-tree models without muscles whose root is the only free joint (identity joint frame), with hinges below it, on
+// one whole wavefront with 4 L lanes.  The tree must be a root with at most four legs of one or two links (Ant); row r of 16
+// lanes then holds the quads  [root (row 0 only) | - | upper link of leg r | lower link of leg r],  so that lower -> upper is a
+// row shift by one quad, the four uppers meet in row 0 through two row folds (Exec::odd_rows, Exec::upper_half) and reach the
+// root by a row shift of two quads.  Quads without a link carry zeros.  dsim_quad_tree_link reads the placement off the model's
+// row-tree step list (level-1 steps: distance = the upper's link; level-2 steps: distance 1) at compile time.
+// The choice depends on the model and on the executor's lane count alone -- never on helper, checkpoint mode or context
+// flavour: every kernel that runs the body level of such a model runs this form.
+template <class D> constexpr int dsim_quad_tree_link(int quad) {   // link of a quad; -1: none; -2: the tree does not fit
+    int up[4] = {-1, -1, -1, -1}, n = 0;
+    for (int s = 0; s < D::RT_N; ++s) {
+        if (D::rt_kind[s] == DSIM_RT_FAR) return -2;
+        if (D::rt_lvl[s] == 1) {
+            if (n == 4) return -2;
+            up[n++] = D::rt_d[s];
+        } else if (D::rt_lvl[s] != 2 || D::rt_d[s] != 1) {
+            return -2;
+        }
+    }
+    int links = 1;
+    for (int r = 0; r < n; ++r) {
+        bool lower = up[r] + 1 < D::L;
+        for (int q = 0; q < n; ++q) lower = lower && up[q] != up[r] + 1;
+        links += lower ? 2 : 1;
+    }
+    if (links != D::L || D::D > 3) return -2;
+    const int row = quad >> 2, slot = quad & 3;
+    if (slot == 0) return row == 0 ? 0 : -1;
+    if (slot == 1 || row >= n) return -1;
+    if (slot == 2) return up[row];
+    bool lower = up[row] + 1 < D::L;
+    for (int q = 0; q < n; ++q) lower = lower && up[q] != up[row] + 1;
+    return lower ? up[row] + 1 : -1;
+}
+template <class Ctx, class Exec> struct DsimQuadBodies {
+    static constexpr bool value = []() {
+        if constexpr (DsimRowTree<Ctx, Exec>::value) {
+            using D = decltype(Ctx::d);
+            bool ok = Exec::WAVE_OPS && D::NS == 0 && Exec::NL == DSIM_NL && 4 * D::L <= Exec::NL && D::D >= 1 && D::D <= 3 &&
+                      D::pmask[0] == DSIM_TM(DSIM_JOINT_FREE) && (D::pident & 1) != 0 && dsim_quad_tree_link<D>(0) == 0;
+            for (int p = 1; p < DSIM_PMASK_N; ++p)
+                ok = ok && (D::pmask[p] & ~(DSIM_TM(DSIM_JOINT_REVOLUTE) | DSIM_TM(DSIM_JOINT_PRISMATIC))) == 0;
+            return ok;
+        } else return false;
+    }();
+};
+// rows 1, 3 of the wavefront's value in rows 0, 2 / rows 2, 3 in rows 0, 1 (what the other rows receive is not used): the device
+// executor has them as v_permlane16_swap / v_permlane32_swap; an executor without those members (the host harness) goes through shfl
+template <class Exec, class = void> struct DsimHasRowFolds : std::false_type {};
+template <class Exec> struct DsimHasRowFolds<Exec, std::void_t<decltype(std::declval<Exec&>().odd_rows(0.f))>> : std::true_type {};
+template <class Exec> DSIM_FN float dsim_odd_rows(Exec& ex, int lane, float v) {
+    if constexpr (DsimHasRowFolds<Exec>::value) return ex.odd_rows(v);
+    else return ex.shfl(v, lane | 16);
+}
+template <class Exec> DSIM_FN float dsim_upper_half(Exec& ex, int lane, float v) {
+    if constexpr (DsimHasRowFolds<Exec>::value) return ex.upper_half(v);
+    else return ex.shfl(v, lane | 32);
+}
+// subtree sum of one register in that layout: root first in the association ((leg 0 + leg 1) + (leg 2 + leg 3)) + root
+template <class Exec> DSIM_FN void dsim_quad_tree_sum(Exec& ex, int lane, float& x) {
+#pragma clang fp contract(off)
+    x = x + ex.template from_above<4>(x);
+    float t = x + dsim_odd_rows(ex, lane, x);
+    t = t + dsim_upper_half(ex, lane, t);
+    x = x + ex.template from_above<8>(t);
+}
 // ADJ: the launch runs adjoint phases (the forward kernels skip the records only those use)
 template <bool ADJ = true, class Ctx, class Exec> DSIM_FN void dsim_topo_init(const Ctx& c, Exec& ex, int lane) {
     if constexpr (DsimTrunk<Ctx, Exec>::value) {
@@ -595,6 +665,21 @@ template <bool ADJ = true, class Ctx, class Exec> DSIM_FN void dsim_topo_init(co
         dsim_quad_consts_init(tp.qc, lane);
         DSIM_OPAQUE(tp.qc.ex); DSIM_OPAQUE(tp.qc.ey); DSIM_OPAQUE(tp.qc.ez);
         DSIM_OPAQUE(tp.qc.kx); DSIM_OPAQUE(tp.qc.ky); DSIM_OPAQUE(tp.qc.kz); DSIM_OPAQUE(tp.qc.qs);
+    }
+    if constexpr (DsimQuadBodies<Ctx, Exec>::value && ADJ) {
+        using D = decltype(c.d);
+        DsimTopoRegs& tp = ex.topo(lane);
+        const int li = dsim_quad_tree_link<D>(lane >> 2);
+        const int i = li >= 0 ? li : 0;
+        tp.qb_i = i;
+        tp.qb_on = li >= 0 ? 1 : 0;
+        tp.qb_type = li >= 0 ? CI(jtype)[i] : -1;
+        tp.qb_cs = CI(qstart)[i];
+        tp.qb_ds = CI(qdstart)[i];
+        if constexpr (!DsimQuadKin<Ctx, Exec::NL>::value) {   // (else: set above)
+            dsim_quad_consts_init(tp.qc, lane);
+            DSIM_OPAQUE(tp.qc.ex); DSIM_OPAQUE(tp.qc.ey); DSIM_OPAQUE(tp.qc.ez); DSIM_OPAQUE(tp.qc.qs);
+        }
     }
     if constexpr (DsimRoleRegs<Ctx, Exec::NL>::value) {
         DsimTopoRegs& tp = ex.topo(lane);
@@ -4057,6 +4142,102 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_bodies(const Ctx& c, Exec
     });
 }
 
+// The main block of dsim_bwd_bodies_rowtree below with four lanes per link (DsimQuadBodies; dsim_math_quad.hpp has the algebra, tools/micro/quad_bwd_block_test.hip
+// both forms side by side): every lane runs the same instructions, quads without a link carry zeros into the three subtree
+// sums, and each set of stores sits under one mask.  Reads and writes the LDS words of the one-link-per-lane block; sums associate by
+// the quad layout's tree steps, so the last bits differ from the one-link-per-lane form.
+template <class Ctx, class Exec> DSIM_FN void dsim_bwd_bodies_quad(const Ctx& c, Exec& ex, int lane, bool update_mass) {
+    static_assert(DsimFreeRootIdent<Ctx>::value, "quad body level: free root with an identity joint frame");
+    const DsimTopoRegs& tp = ex.topo(lane);
+    typedef DsimQuadLanes<Exec> B;
+    typedef DsimQuadSv<B> Sv;
+    const B b(ex, lane, tp.qc);
+    int type = tp.qb_type;
+    DSIM_OPAQUE(type);
+    const bool on = tp.qb_on != 0, fr = type == DSIM_JOINT_FREE, hinge = type == DSIM_JOINT_PRISMATIC || type == DSIM_JOINT_REVOLUTE;
+    const int i = tp.qb_i, cs = tp.qb_cs, ds = tp.qb_ds, cc = lane & 3;
+    // ---- every operand that does not come out of this phase, in one round trip
+    const DsimQuadI<B> I = dq_ld_i10(b, WF(i10) + 10 * i);
+    const Sv v = dq_ldsv(b, WF(v) + 6 * i), a = dq_ldsv(b, WF(a) + 6 * i), r = dq_ldsv(b, WF(af) + 6 * i);
+    const float grav = b.template ld<3>(CF(grav));
+    DsimQuadG<B> g = dq_ld_g10(b, WF(ai10m) + 10 * i);
+    if (!update_mass) g = dq_g10_zero(b);
+    const Sv S0 = dq_ldsv(b, WF(S) + 6 * ds), aS0 = dq_ldsv(b, WF(aS) + 6 * ds);
+    float* aq = WF(aq);
+    float* aqd = WF(aqd);
+    // hinge: the word of its dof / coordinate in every lane; free root: words c and 3 + c of its six dofs / seven coordinates
+    const int dl = fr ? (cc < 3 ? cc : 2) : 0;
+    const Sv qd6{WF(qd)[ds + dl], b.template ld<3>(WF(qd) + ds + 3)}, g6{aqd[ds + dl], b.template ld<3>(aqd + ds + 3)};
+    const float qd0 = qd6.w, g0 = g6.w, gp = aq[cs + dl];
+    const float pc = b.template ld<3>(WF(xsc) + 7 * i), rc = b.template ld<4>(WF(xsc) + 7 * i + 3), gr = b.template ld<4>(aq + cs + 3);
+    ex.loads_landed();
+    // ---- f^T, velocity / acceleration recursions^T of the link itself, pose wrench of inertia + gravity
+    const Sv hv = dq_inertia_mul(b, I, v);
+    Sv av_t = dq_fcross_t(b, hv, r);
+    const Sv ahv = dq_unrot(b, dq_scross_t(b, r, v));
+    Sv av = dq_inertia_mul(b, I, ahv);
+#ifdef DSIM_INJECT_ADJ_ERROR
+    av = dq_sv_scale(b, av, DSIM_INJECT_ADJ_ERROR);   // (developer / test builds only, see dsim_bwd_bodies)
+    av_t = dq_sv_scale(b, av_t, DSIM_INJECT_ADJ_ERROR);
+#endif
+    dq_inertia_bilinear_adj(b, g, r, a);
+    dq_inertia_bilinear_adj(b, g, ahv, v);
+    g.ht = dq_cross_t_acc(b, g.ht, r.w, grav);   // gravity: h x (r.w x grav), m (r.w x grav)
+    DsimQuadWrenchT<B> W = dq_inertia_pose_wrench(b, I, g);
+    Sv A = dq_inertia_mul(b, I, r);   // aa
+    if (!on) {
+        A.w = 0.f; A.v = 0.f;
+        W.wt = 0.f; W.v = 0.f;
+    }
+    // ---- aatot = subtree sum of aa; joint motion^T
+    dsim_quad_tree_sum(ex, lane, A.w);
+    dsim_quad_tree_sum(ex, lane, A.v);
+    Sv vj = dq_sv_scale(b, S0, qd0);
+    if (fr) vj = qd6;
+    av_t = dq_scross_dual_t_acc(b, av_t, vj, A);
+    const Sv avj_t = dq_fcross_t(b, A, v);
+    ex.stamp();
+    // ---- the contact terms of the own body, reduced per body by the side block
+    ex.side_done();
+    const Sv cpose = dq_ldsv(b, WF(agx) + 12 * i), ctw = dq_ldsv(b, WF(agx) + 12 * i + 6);
+    ex.loads_landed();
+    // ---- avtot = subtree sum of (a_v + contact twist cotangents); cotangents of qd and of S
+    Sv T = dq_sv_add(b, dq_unrot_add(b, av, av_t), ctw);
+    if (!on) {
+        T.w = 0.f; T.v = 0.f;
+    }
+    dsim_quad_tree_sum(ex, lane, T.w);
+    dsim_quad_tree_sum(ex, lane, T.v);
+    const Sv avj = dq_unrot_add(b, T, avj_t);
+    Sv Wp_t = dq_scross_dual_t(b, S0, dq_sv_axpy(b, avj, qd0, aS0));
+    if (!hinge) {
+        Wp_t.w = 0.f; Wp_t.v = 0.f;
+    }
+    const float aqd_new = b.add(g0, dq_sdot(b, S0, avj));
+    // ---- azs = subtree sum of the pose wrenches (inertia + gravity, joint frame of the children's S, contacts)
+    Sv Z;
+    Z.w = b.add(cpose.w, b.template perm<DSIM_QP_YZXW>(b.add(W.wt, Wp_t.w)));
+    Z.v = b.add(cpose.v, b.add(W.v, b.template perm<DSIM_QP_YZXW>(Wp_t.v)));
+    if (!on) {
+        Z.w = 0.f; Z.v = 0.f;
+    }
+    dsim_quad_tree_sum(ex, lane, Z.w);
+    dsim_quad_tree_sum(ex, lane, Z.v);
+    const Sv Wt = dq_unrot_sub(b, Z, Wp_t);   // without the part attached to the link's own joint frame
+    ex.stamp();
+    // ---- adj q_d = S_d . Wt (hinge), pose cotangent of the free root; all stores of the phase
+    const float aq_new = b.add(gp, dq_sdot(b, S0, Wt));
+    const Sv aqd6 = dq_sv_add(b, g6, avj);
+    const float tc = dq_cross_sub(b, Wt.w, pc, Wt.v);
+    const float aqp = b.add(gp, Wt.v), aqr = b.fma(dq_qmul_v(b, tc, rc), 2.f, gr);
+    if (on && (cc == 0 || (fr && cc < 3))) {
+        aqd[ds + cc] = fr ? aqd6.w : aqd_new;
+        aq[cs + cc] = fr ? aqp : aq_new;
+    }
+    if (fr && cc < 3) aqd[ds + 3 + cc] = aqd6.v;
+    if (fr) aq[cs + 3 + cc] = aqr;
+}
+
 // Body level of the adjoint substep for row trees (DsimRowTree): ONE phase on the link lanes.  dsim_bwd_bodies below is the
 // general form -- per-link block, subtree sum, per-link block, subtree sum, per-link block, subtree sum, per-link block: seven
 // phases, each paying an LDS round trip for values that only change lanes inside the tree.  Here the three subtree sums are
@@ -4319,7 +4500,7 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_bodies_rowtree(const Ctx&
         });
         ex.run_wave0(fm);
     } else {
-        ex.fork_side(fm, [&](int lane) {
+        auto side = [&](int lane) __attribute__((always_inline)) {
             // side block: contacts^T per contact, then the per-body sums of their 12-float rows (bodies without contacts: zeros)
             dsim_bwd_external_items(c, ex, lane);
             ex.lds_fence();
@@ -4340,7 +4521,13 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_bodies_rowtree(const Ctx&
                 const int it = lane + Exec::NL * p;
                 if (it < 12 * L) WF(agx)[it] = acc;
             }
-        });
+        };
+        if constexpr (DsimQuadBodies<Ctx, Exec>::value) {
+            auto fmq = [&](int lane) __attribute__((always_inline)) { dsim_bwd_bodies_quad(c, ex, lane, update_mass); };
+            ex.fork_side(fmq, side);
+        } else {
+            ex.fork_side(fm, side);
+        }
     }
 }
 

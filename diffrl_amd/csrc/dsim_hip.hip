@@ -292,6 +292,18 @@ template <int NW, int PF = 6, int CW = 0, bool HELPER = false, int EPW = 1> stru
         static_assert(P >= 0 && P <= 0xff, "quad_perm: four two-bit selectors");
         return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), P, 0xf, 0xf, true));
     }
+    // rows 1, 3 of v in rows 0, 2 (v_permlane16_swap: the odd rows of the first operand change places with the even rows of the
+    // second; both operands are v) and rows 2, 3 in rows 0, 1 (v_permlane32_swap): the row folds of the quad body level's subtree
+    // sums (dsim_core.hpp: dsim_quad_tree_sum).  VALU latency, no LDS; builtins, so the compiler places the hazard waits.  One
+    // environment per wavefront only.  Pinned on hardware by tools/micro/dpp_semantics.hip (profiles/quad_adjoint_ab.txt has its output).
+    __device__ __forceinline__ float odd_rows(float v) {
+        static_assert(EPW == 1, "row folds span the whole wavefront");
+        return __int_as_float(__builtin_amdgcn_permlane16_swap(__float_as_int(v), __float_as_int(v), false, false)[1]);
+    }
+    __device__ __forceinline__ float upper_half(float v) {
+        static_assert(EPW == 1, "row folds span the whole wavefront");
+        return __int_as_float(__builtin_amdgcn_permlane32_swap(__float_as_int(v), __float_as_int(v), false, false)[1]);
+    }
     // a_k += a_k[lane + D of the row] * w for six values at once: v_fmac_f32 with the DPP shift ON ITS OPERAND (the compiler
     // keeps a v_mov_b32_dpp + v_fmac pair for the builtin form: twice the instructions on a path where every issue slot counts).
     // A VGPR written by a VALU instruction may be read through DPP two wait states later at the earliest: the six lines are

@@ -97,6 +97,10 @@ struct DsimQuadScalar {
 #pragma unroll
         for (int k = N0; k < N; ++k) p[k] = a.c[k];
     }
+    // row R of a symmetric 3 x 3 matrix kept as six words s = (xx, xy, xz, yy, yz, zz): (xx, xy, xz), (xy, yy, yz), (xz, yz, zz)
+    template <int R> DSIM_MFN T ld_sym(const float* s) const {
+        return R == 0 ? T{{s[0], s[1], s[2], 0.f}} : R == 1 ? T{{s[1], s[3], s[4], 0.f}} : T{{s[2], s[4], s[5], 0.f}};
+    }
     DSIM_MFN bool xyz() const { return true; }
     // lane constants
     DSIM_MFN T ex() const { return lanes(1.f, 0.f, 0.f, 0.f); }
@@ -153,6 +157,10 @@ template <class Exec> struct DsimQuadLanes {
     template <int N> DSIM_MFN void st(float* p, T a) const { p[c] = a; }
     template <int N0, int N> DSIM_MFN void st_from(float* p, T a) const {
         if (c >= N0) p[c] = a;
+    }
+    // (per-lane word of the row; the w lane re-reads the z lane's)
+    template <int R> DSIM_MFN T ld_sym(const float* s) const {
+        return s[R == 0 ? (c < 3 ? c : 2) : R == 1 ? (c == 0 ? 1 : c == 1 ? 3 : 4) : (c == 0 ? 2 : c == 1 ? 4 : 5)];
     }
     DSIM_MFN bool xyz() const { return c < 3; }
     DSIM_MFN T ex() const { return k.ex; }
@@ -312,4 +320,118 @@ DSIM_FN DsimQuadBody<B> dq_body_inertia_force(const B& b, typename B::T rc, type
     r.f.w = dq_cross_acc(b, fb.w, mg, cm);
     r.f.v = b.sub(fb.v, mg);
     return r;
+}
+
+// ---- the adjoint's body level (dsim_core.hpp: dsim_bwd_bodies_rowtree) ---------------------------------------------------------
+// Sums of cross products stay in the ROTATED frame of dq_cross_t (t = (c_z, c_x, c_y)) for as long as they are only added to:
+// dq_cross_t_acc chains them at two instructions each, and the one permutation back rides on the add or subtract that
+// consumes the sum (dq_unrot_add / dq_unrot_sub).  A DsimQuadSv whose name ends in _t holds both halves in that frame.
+template <class B> DSIM_FN DsimQuadSv<B> dq_ldsv(const B& b, const float* p) {
+    DsimQuadSv<B> x;
+    x.w = b.template ld<3>(p);
+    x.v = b.template ld<3>(p + 3);
+    return x;
+}
+template <class B> DSIM_FN DsimQuadSv<B> dq_sv_add(const B& b, const DsimQuadSv<B>& a, const DsimQuadSv<B>& x) {
+    return DsimQuadSv<B>{b.add(a.w, x.w), b.add(a.v, x.v)};
+}
+template <class B> DSIM_FN DsimQuadSv<B> dq_unrot(const B& b, const DsimQuadSv<B>& t) {
+    return DsimQuadSv<B>{b.template perm<DSIM_QP_YZXW>(t.w), b.template perm<DSIM_QP_YZXW>(t.v)};
+}
+template <class B> DSIM_FN DsimQuadSv<B> dq_unrot_add(const B& b, const DsimQuadSv<B>& acc, const DsimQuadSv<B>& t) {
+    return DsimQuadSv<B>{b.add(acc.w, b.template perm<DSIM_QP_YZXW>(t.w)), b.add(acc.v, b.template perm<DSIM_QP_YZXW>(t.v))};
+}
+template <class B> DSIM_FN DsimQuadSv<B> dq_unrot_sub(const B& b, const DsimQuadSv<B>& acc, const DsimQuadSv<B>& t) {
+    return DsimQuadSv<B>{b.sub(acc.w, b.template perm<DSIM_QP_YZXW>(t.w)), b.sub(acc.v, b.template perm<DSIM_QP_YZXW>(t.v))};
+}
+// S s and S s + y (joint motion: S_d qd_d; cotangent of S: aS + a_vj qd)
+template <class B> DSIM_FN DsimQuadSv<B> dq_sv_scale(const B& b, const DsimQuadSv<B>& a, float s) {
+    return DsimQuadSv<B>{dq_scale(b, a.w, s), dq_scale(b, a.v, s)};
+}
+template <class B> DSIM_FN DsimQuadSv<B> dq_sv_axpy(const B& b, const DsimQuadSv<B>& a, float s, const DsimQuadSv<B>& y) {
+    return DsimQuadSv<B>{dq_axpy(b, a.w, s, y.w), dq_axpy(b, a.v, s, y.v)};
+}
+// spatial inertia from the 10 words (m, h, xx, xy, xz, yy, yz, zz) of dsim_math.hpp's inertia10
+template <class B> DSIM_FN DsimQuadI<B> dq_ld_i10(const B& b, const float* p) {
+    DsimQuadI<B> I;
+    I.m = p[0];
+    I.h = b.template ld<3>(p + 1);
+    I.r0 = b.template ld_sym<0>(p + 4);
+    I.r1 = b.template ld_sym<1>(p + 4);
+    I.r2 = b.template ld_sym<2>(p + 4);
+    return I;
+}
+// a x x for motion vectors (dsim_math.hpp: scross), rotated frame
+template <class B> DSIM_FN DsimQuadSv<B> dq_scross_t(const B& b, const DsimQuadSv<B>& a, const DsimQuadSv<B>& x) {
+    return DsimQuadSv<B>{dq_cross_t(b, a.w, x.w), dq_cross_t_acc(b, dq_cross_t(b, a.v, x.w), a.w, x.v)};
+}
+// a x* x (scross_dual), rotated frame; ... added to t
+template <class B> DSIM_FN DsimQuadSv<B> dq_scross_dual_t(const B& b, const DsimQuadSv<B>& a, const DsimQuadSv<B>& x) {
+    return DsimQuadSv<B>{dq_cross_t_acc(b, dq_cross_t(b, a.w, x.w), a.v, x.v), dq_cross_t(b, a.w, x.v)};
+}
+template <class B>
+DSIM_FN DsimQuadSv<B> dq_scross_dual_t_acc(const B& b, const DsimQuadSv<B>& t, const DsimQuadSv<B>& a, const DsimQuadSv<B>& x) {
+    return DsimQuadSv<B>{dq_cross_t_acc(b, dq_cross_t_acc(b, t.w, a.w, x.w), a.v, x.v), dq_cross_t_acc(b, t.v, a.w, x.v)};
+}
+// the cross-product pairs of f^T: cotangent of x in  y . (x x* f)  for a force f and a motion cotangent y -- written with the
+// operands the way the phase has them,  (f.w x y.w + f.v x y.v,  f.v x y.w) = -(y x* f); rotated frame
+template <class B> DSIM_FN DsimQuadSv<B> dq_fcross_t(const B& b, const DsimQuadSv<B>& f, const DsimQuadSv<B>& y) {
+    return DsimQuadSv<B>{dq_cross_t_acc(b, dq_cross_t(b, f.w, y.w), f.v, y.v), dq_cross_t(b, f.v, y.w)};
+}
+// a . x of two spatial vectors, in components x, y, z (each lane adds the three pair products in its own cyclic order, dq_dot3)
+template <class B> DSIM_FN typename B::T dq_sdot(const B& b, const DsimQuadSv<B>& a, const DsimQuadSv<B>& x) {
+    const typename B::T p = b.fma(a.v, x.v, b.mul(a.w, x.w));
+    return b.add(b.add(p, b.template perm<DSIM_QP_YZXW>(p)), b.template perm<DSIM_QP_ZXYW>(p));
+}
+// (a, 0) (x) x for a 3-vector a (dsim_math.hpp: qmul_v): dq_qmul without the term of a's w component, which is not read
+template <class B> DSIM_FN typename B::T dq_qmul_v(const B& b, typename B::T a, typename B::T x) {
+    typename B::T r = b.mul(b.mul(b.template perm<DSIM_QP_XYZX>(a), b.qs()), b.template perm<DSIM_QP_WWWX>(x));
+    r = b.fma(b.mul(b.template perm<DSIM_QP_YZXY>(a), b.qs()), b.template perm<DSIM_QP_ZXYY>(x), r);
+    return b.nfma(b.template perm<DSIM_QP_ZXYZ>(a), b.template perm<DSIM_QP_YZXZ>(x), r);
+}
+// Cotangent of a spatial inertia's 10 parameters (dsim_math.hpp: g[10]; the mass word is never needed).  The six words of the
+// symmetric block are held as the three rows of G + G^T, G the cotangent of A's nine entries: the off-diagonal entries are the
+// words themselves, the diagonal carries TWICE its word -- which is the matrix the pose wrench wants (dsim_core.hpp:
+// inertia_pose_wrench, G2).  The first-moment part is h + (ht out of the rotated frame): ht collects cross products.  The body
+// level only READS the cotangent from LDS (ai10m, dq_ld_g10) and consumes it as a pose wrench: no kernel stores this form.
+template <class B> struct DsimQuadG {
+    typename B::T h, ht, r0, r1, r2;
+};
+template <class B> DSIM_FN DsimQuadG<B> dq_g10_zero(const B& b) {
+    const typename B::T z = b.spl(0.f);
+    return DsimQuadG<B>{z, z, z, z, z};
+}
+template <class B> DSIM_FN DsimQuadG<B> dq_ld_g10(const B& b, const float* p) {
+    DsimQuadG<B> g;
+    g.h = b.template ld<3>(p + 1);
+    g.ht = b.spl(0.f);
+    const typename B::T r0 = b.template ld_sym<0>(p + 4), r1 = b.template ld_sym<1>(p + 4), r2 = b.template ld_sym<2>(p + 4);
+    g.r0 = b.fma(r0, b.ex(), r0);
+    g.r1 = b.fma(r1, b.ey(), r1);
+    g.r2 = b.fma(r2, b.ez(), r2);
+    return g;
+}
+// g += cotangent of y^T I x (dsim_math.hpp: inertia_bilinear_adj with weight 1):  G + G^T += y.w x.w^T + x.w y.w^T,
+// g_h += x.v x y.w + y.v x x.w
+template <class B> DSIM_FN void dq_inertia_bilinear_adj(const B& b, DsimQuadG<B>& g, const DsimQuadSv<B>& y, const DsimQuadSv<B>& x) {
+    g.ht = dq_cross_t_acc(b, dq_cross_t_acc(b, g.ht, x.v, y.w), y.v, x.w);
+    g.r0 = b.fma(y.w, b.template perm<DSIM_QP_XXXX>(x.w), b.fma(x.w, b.template perm<DSIM_QP_XXXX>(y.w), g.r0));
+    g.r1 = b.fma(y.w, b.template perm<DSIM_QP_YYYY>(x.w), b.fma(x.w, b.template perm<DSIM_QP_YYYY>(y.w), g.r1));
+    g.r2 = b.fma(y.w, b.template perm<DSIM_QP_ZZZZ>(x.w), b.fma(x.w, b.template perm<DSIM_QP_ZZZZ>(y.w), g.r2));
+}
+// g as a pose wrench (dsim_core.hpp: inertia_pose_wrench): torque = sum_k A_k x (G + G^T)_k + h x g_h over the rows k (rotated
+// frame), force = tr(G + G^T) h - (G + G^T) h + m g_h.  A term u x grav of the gravity wrench joins g_h before the call
+// (g.ht = dq_cross_t_acc(b, g.ht, u, grav)): both are h x . and m . of their sum.
+template <class B> struct DsimQuadWrenchT {
+    typename B::T wt, v;   // torque in the rotated frame, force
+};
+template <class B> DSIM_FN DsimQuadWrenchT<B> dq_inertia_pose_wrench(const B& b, const DsimQuadI<B>& I, const DsimQuadG<B>& g) {
+    typedef typename B::T T;
+    const T gh = b.add(g.h, b.template perm<DSIM_QP_YZXW>(g.ht));
+    DsimQuadWrenchT<B> W;
+    W.wt = dq_cross_t_acc(b, dq_cross_t_acc(b, dq_cross_t_acc(b, dq_cross_t(b, I.r0, g.r0), I.r1, g.r1), I.r2, g.r2), I.h, gh);
+    const T d = b.fma(g.r2, b.ez(), b.fma(g.r1, b.ey(), b.mul(g.r0, b.ex())));
+    const T tr = b.add(b.add(d, b.template perm<DSIM_QP_YZXW>(d)), b.template perm<DSIM_QP_ZXYW>(d));
+    W.v = b.fma(gh, b.spl(I.m), b.sub(b.mul(I.h, tr), dq_sym_mul(b, g.r0, g.r1, g.r2, I.h)));
+    return W;
 }

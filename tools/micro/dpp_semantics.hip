@@ -1,5 +1,6 @@
 // Developer micro-test (GPU box): pins the semantics of the DPP row shifts the row-tree sums of dsim_core.hpp rely on
-// (dsim_hip.hip: DevExec::row_from_above / row_from_below).  hipcc --offload-arch=gfx950 -O2 dpp_semantics.hip -o dpp_semantics
+// (dsim_hip.hip: DevExec::row_from_above / row_from_below), of the row shifts by one and two quads and of the row folds of the
+// quad body level's subtree sums (DevExec::odd_rows / upper_half).  hipcc --offload-arch=gfx950 -O2 dpp_semantics.hip -o dpp_semantics
 #include <hip/hip_runtime.h>
 #include <cstdio>
 
@@ -17,20 +18,27 @@ __global__ void k(int* out) {
     out[4 * 64 + lane] = r;
     out[5 * 64 + lane] = dpp<0x130, false>(-1, v);   // wave_shl:1
     out[6 * 64 + lane] = dpp<0x138, false>(-1, v);   // wave_shr:1
+    out[7 * 64 + lane] = dpp<0x104, true>(-1, v);    // row_shl:4, bound_ctrl on: the next quad of the row, 0 in the row's last quad
+    out[8 * 64 + lane] = dpp<0x108, true>(-1, v);    // row_shl:8, bound_ctrl on
+    out[9 * 64 + lane] = __builtin_amdgcn_permlane16_swap(v, v, false, false)[1];    // expected: rows 0, 2 hold rows 1, 3 of v
+    out[10 * 64 + lane] = __builtin_amdgcn_permlane32_swap(v, v, false, false)[1];   // expected: rows 0, 1 hold rows 2, 3 of v
 }
+
+constexpr int NT = 11;
 
 int main() {
     int* d;
-    hipMalloc(&d, 7 * 64 * 4);
+    hipMalloc(&d, NT * 64 * 4);
     hipLaunchKernelGGL(k, 1, 64, 0, 0, d);
-    int h[7 * 64];
+    int h[NT * 64];
     hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
-    const char* names[7] = {"row_shl:1 old=-1 bc=0", "row_shr:1 old=-1 bc=0", "row_shl:8 old=-1 bc=0", "row_shl:1 old=-1 bc=1",
-                            "row_shl:1, lane 5 disabled", "wave_shl:1", "wave_shr:1"};
-    for (int t = 0; t < 7; ++t) {
+    const char* names[NT] = {"row_shl:1 old=-1 bc=0", "row_shr:1 old=-1 bc=0", "row_shl:8 old=-1 bc=0", "row_shl:1 old=-1 bc=1",
+                             "row_shl:1, lane 5 disabled", "wave_shl:1", "wave_shr:1", "row_shl:4 old=-1 bc=1", "row_shl:8 old=-1 bc=1",
+                             "permlane16_swap(v, v)[1]", "permlane32_swap(v, v)[1]"};
+    for (int t = 0; t < NT; ++t) {
         printf("%-28s:", names[t]);
         for (int l = 0; l < 20; ++l) printf(" %d", h[t * 64 + l]);
-        printf(" ... l63=%d\n", h[t * 64 + 63]);
+        printf(" ... l32=%d l48=%d l63=%d\n", h[t * 64 + 32], h[t * 64 + 48], h[t * 64 + 63]);
     }
     return 0;
 }
