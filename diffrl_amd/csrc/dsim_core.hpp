@@ -2323,6 +2323,29 @@ template <class Ctx, class Exec> struct DsimSavedIl {
         }
     }();
 };
+// The free root's share of the integrator and of integrate^T (dsim_bwd_joint_wave) in the quad form of dsim_math_quad.hpp
+// (dq_root_integrate, dq_root_integrate_adj): the models of the fused joint-space adjoint -- a free root with six dofs on lanes
+// 0 .. 5, one hinge per other link, at most DSIM_JW_ND_MAX dofs (Ant) -- whose kernels keep the quad lane constants (DsimQuadKin).
+// QUAD: the root's 3- and 4-vectors sit on lanes 0 .. 3, one component per lane (link 0's quad of the kinematics layout); the
+// angular dofs 0 .. 2 are those lanes' own, the linear dofs 3 .. 5 come and go by one row shift.  Every quad of the wave runs
+// the same instructions on the same addresses (the permutations need all four lanes), quad 0 alone stores.  Otherwise (two
+// environments per wavefront) lane 0 runs the scalar backend of the same source: the same bits.
+#define DSIM_JW_ND_MAX 16
+template <class Ctx, class Exec> struct DsimQuadRoot {
+    static constexpr bool value = []() {
+        if constexpr (DsimWaveDyn<Ctx, Exec>::value && DsimDofShift<Ctx, Exec>::value && DsimQuadKin<Ctx, Exec::NL>::value) {
+            using D = decltype(Ctx::d);
+            return D::JW_OK != 0 && D::JW_FREE_ROOT != 0 && D::ND_ROOT == 6 && D::nd <= DSIM_JW_ND_MAX && D::nd <= Exec::NL &&
+                   (D::tmask & DSIM_TM(DSIM_JOINT_BALL)) == 0;
+        } else {
+            return false;
+        }
+    }();
+    static constexpr bool QUAD = []() {
+        if constexpr (value) return DsimQuadKin<Ctx, Exec::NL>::QUAD;
+        else return false;
+    }();
+};
 template <class Ctx, class Exec>
 DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float* g_hinv, bool update_mass) {
     ex.mark(3);
@@ -2340,6 +2363,8 @@ DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float*
     ex.fork_mid_detached([&](int lane) {
         constexpr int MASK = dsim_tmask_static<Ctx>();
         constexpr int NQ = dsim_mask_nq(MASK), NDF = dsim_mask_nd(MASK);
+        constexpr bool QR = DsimQuadRoot<Ctx, Exec>::value, QRL = DsimQuadRoot<Ctx, Exec>::QUAD;
+        constexpr int NQL = QRL ? 1 : NQ, NDL = QRL ? 1 : NDF;   // (quad root: a link lane holds its hinge's words alone)
         const float h = c.h;
         const DsimTopoRegs& tp = ex.topo(lane);
         const bool is_dof = lane < nd, is_link = lane < L;
@@ -2363,9 +2388,16 @@ DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float*
         const int lcs = tp.own_cs, lds_ = tp.own_ds;
         float qv[NQ > 0 ? NQ : 1], qdv[NDF > 0 ? NDF : 1];
 #pragma unroll
-        for (int k = 0; k < NQ; ++k) qv[k] = WF(q)[lcs + k];
+        for (int k = 0; k < NQL; ++k) qv[k] = WF(q)[lcs + k];
 #pragma unroll
-        for (int k = 0; k < NDF; ++k) qdv[k] = WF(qd)[lds_ + k];
+        for (int k = 0; k < NDL; ++k) qdv[k] = WF(qd)[lds_ + k];
+        // quad root: position, rotation and twist of link 0, one component per lane
+        [[maybe_unused]] float rq_p = 0.f, rq_r = 0.f, rq_w = 0.f, rq_v = 0.f;
+        if constexpr (QRL) {
+            const DsimQuadLanes<Exec> b(ex, lane, tp.qc);
+            rq_p = dq_ld3(b, WF(q)); rq_r = dq_ldq(b, WF(q) + 3);
+            rq_w = dq_ld3(b, WF(qd)); rq_v = dq_ld3(b, WF(qd) + 3);
+        }
         sv6 F;
         if constexpr (DsimRowTreeFwd<Ctx, Exec>::value && DsimWaveDyn<Ctx, Exec>::sums_inside) {
             // ---- link role: f_tot = row-tree subtree sums on registers; f_tot[link(d)] -> dof lane d
@@ -2421,7 +2453,10 @@ DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float*
         ex.stamp();
         // ---- qdd of a link's dofs -> the link's lane
         float av[NDF > 0 ? NDF : 1];
-        if constexpr (DsimDofShift<Ctx, Exec>::value) {
+        if constexpr (QRL) {
+            // link lane l <- dof lane l + DSH (its one dof); the root's quad reads the dof lanes themselves (below)
+            av[0] = dsim_row_shift<-D::DSH>(ex, acc);
+        } else if constexpr (DsimDofShift<Ctx, Exec>::value) {
             // link lane l <- dof lane l + DSH (its one dof); the root <- its ND_ROOT dofs on lanes 0 .. ND_ROOT - 1 (v_readlane)
 #pragma unroll
             for (int k = 0; k < NDF; ++k) av[k] = (k < D::ND_ROOT) ? ex.bcast(acc, k < D::ND_ROOT ? k : 0) : 0.f;
@@ -2441,6 +2476,51 @@ DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float*
         if (hinge_l) {
             qdn = qdv[0] + av[0] * h;
             qn = qv[0] + qdn * h;
+        }
+        if constexpr (QR) {
+            // ---- the free root in the quad form.  QUAD: qdd of the angular dofs is lanes 0 .. 2's own, that of the linear dofs
+            // comes down from lanes 3 .. 5 by one row shift; results go out by per-lane address from quad 0
+            if constexpr (QRL) {
+                const DsimQuadLanes<Exec> b(ex, lane, tp.qc);
+                const DsimQuadRootStep<DsimQuadLanes<Exec>> rs =
+                    dq_root_integrate(b, rq_p, rq_r, rq_w, rq_v, acc, ex.template from_above<3>(acc), h);
+                if constexpr (DsimSavedIl<Ctx, Exec>::value) {
+                    if (lane == 0) WF(qil)[0] = rs.il;
+                }
+                ex.mid();
+                ex.stamp();
+                if (is_link && hinge_l) {
+                    WF(qd)[lds_] = qdn;
+                    WF(q)[lcs] = qn;
+                }
+                if (lane < 4) {
+                    dq_st3(b, WF(q), rs.pn);
+                    dq_stq(b, WF(q) + 3, rs.rn);
+                    dq_st3(b, WF(qd), rs.w);
+                    dq_st3(b, WF(qd) + 3, rs.vn);
+                }
+            } else {
+                const DsimQuadScalar b;
+                DsimQuadRootStep<DsimQuadScalar> rs{};
+                if (is_link && fr) {
+                    rs = dq_root_integrate(b, dq4{{qv[0], qv[1], qv[2], 0.f}}, dq4{{qv[3], qv[4], qv[5], qv[6]}}, dq4{{qdv[0], qdv[1], qdv[2], 0.f}},
+                                           dq4{{qdv[3], qdv[4], qdv[5], 0.f}}, dq4{{av[0], av[1], av[2], 0.f}}, dq4{{av[3], av[4], av[5], 0.f}}, h);
+                    if constexpr (DsimSavedIl<Ctx, Exec>::value) WF(qil)[0] = rs.il;
+                }
+                ex.mid();
+                ex.stamp();
+                if (is_link && hinge_l) {
+                    WF(qd)[lds_] = qdn;
+                    WF(q)[lcs] = qn;
+                }
+                if (is_link && fr) {
+                    dq_st3(b, WF(q) + lcs, rs.pn);
+                    dq_stq(b, WF(q) + lcs + 3, rs.rn);
+                    dq_st3(b, WF(qd) + lds_, rs.w);
+                    dq_st3(b, WF(qd) + lds_ + 3, rs.vn);
+                }
+            }
+            return;
         }
         if constexpr ((MASK & (DSIM_TM(DSIM_JOINT_BALL) | DSIM_TM(DSIM_JOINT_FREE))) != 0) {
             if (quat_l) {
@@ -3214,7 +3294,6 @@ template <class Ctx, class Exec> DSIM_FN void dsim_hacc_zero(const Ctx& c, Exec&
 // v_readlane; adj qdd then travels by v_readlane into the rows of H^-1 each dof lane holds in registers (the mirror of the
 // forward's qdd = H^-1 tau), and adj tau stays in the register the per-dof block needs it in.  Two phase boundaries and the LDS
 // round trips of adj qdd and adj tau leave the critical path; same operations in the same order as the three phases.
-#define DSIM_JW_ND_MAX 16
 template <class Ctx, class Exec> struct DsimJointWave {
     static constexpr bool value = []() {
         if constexpr (std::is_empty<decltype(Ctx::d)>::value && Exec::WAVE_OPS) {
@@ -3252,7 +3331,47 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_wave(const Ctx& c, 
         const float g_q = WF(aq)[qi], g_qd_in = WF(aqd)[d], g_act = WF(aact)[d];
         // ---- integrate^T: the free root on lane 0 (its six new adj qd values in r6), a hinge on its dof lane
         float r6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if constexpr (D::JW_FREE_ROOT != 0) {
+        constexpr bool QR = DsimQuadRoot<Ctx, Exec>::value, QRL = DsimQuadRoot<Ctx, Exec>::QUAD;
+        [[maybe_unused]] float rq_gw = 0.f, rq_gv = 0.f;
+        if constexpr (QRL) {
+            // the free root on quad 0, one component per lane (every quad runs the same instructions on the same addresses, quad 0
+            // stores).  The incoming adj qd of the angular dofs is lanes 0 .. 2's own g_qd_in, that of the linear dofs comes
+            // down from lanes 3 .. 5 by one row shift.
+            const DsimQuadLanes<Exec> b(ex, lane, tp.qc);
+            const float p = dq_ld3(b, WF(q)), r = dq_ldq(b, WF(q) + 3), g_pn = dq_ld3(b, WF(aq)), g_rn = dq_ldq(b, WF(aq) + 3);
+            const float w = dq_axpy(b, dq_ld3(b, WF(qdd)), h, dq_ld3(b, WF(qd)));
+            const float rt = dq_root_rt(b, r, w, h);
+            float il;
+            if constexpr (DsimSavedIl<Ctx, Exec>::value) il = WF(qil)[0];   // from the forward launch, through the checkpoint
+            else il = dq_root_il(b, rt);
+            const DsimQuadRootAdj<DsimQuadLanes<Exec>> ra =
+                dq_root_integrate_adj(b, p, r, w, rt, il, g_pn, g_rn, g_qd_in, ex.template from_above<3>(g_qd_in), h);
+            if (lane < 4) {
+                dq_st3(b, WF(aq), ra.aq_p);
+                dq_stq(b, WF(aq) + 3, ra.aq_r);
+            }
+            rq_gw = ra.g_w;
+            rq_gv = ex.template from_below<3>(ra.g_v);   // g_v of lanes 0 .. 2 -> the linear dofs' lanes 3 .. 5
+        } else if constexpr (QR) {
+            int ltype = tp.own_type;
+            DSIM_OPAQUE(ltype);
+            if (lane < D::L && ltype == DSIM_JOINT_FREE) {
+                const DsimQuadScalar b;
+                const int lcs = tp.own_cs, lds_ = tp.own_ds;
+                const dq4 p = dq_ld3(b, WF(q) + lcs), r = dq_ldq(b, WF(q) + lcs + 3), g_pn = dq_ld3(b, WF(aq) + lcs), g_rn = dq_ldq(b, WF(aq) + lcs + 3);
+                const dq4 w = dq_axpy(b, dq_ld3(b, WF(qdd) + lds_), h, dq_ld3(b, WF(qd) + lds_));
+                const dq4 rt = dq_root_rt(b, r, w, h);
+                float il;
+                if constexpr (DsimSavedIl<Ctx, Exec>::value) il = WF(qil)[0];
+                else il = dq_root_il(b, rt);
+                const DsimQuadRootAdj<DsimQuadScalar> ra =
+                    dq_root_integrate_adj(b, p, r, w, rt, il, g_pn, g_rn, dq_ld3(b, WF(aqd) + lds_), dq_ld3(b, WF(aqd) + lds_ + 3), h);
+                dq_st3(b, WF(aq) + lcs, ra.aq_p);
+                dq_stq(b, WF(aq) + lcs + 3, ra.aq_r);
+                r6[0] = ra.g_w.c[0]; r6[1] = ra.g_w.c[1]; r6[2] = ra.g_w.c[2];
+                r6[3] = ra.g_v.c[0]; r6[4] = ra.g_v.c[1]; r6[5] = ra.g_v.c[2];
+            }
+        } else if constexpr (D::JW_FREE_ROOT != 0) {
             int ltype = tp.own_type;
             DSIM_OPAQUE(ltype);
             if (lane < D::L && ltype == DSIM_JOINT_FREE) {
@@ -3289,7 +3408,9 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_wave(const Ctx& c, 
             }
         }
         float g = g_qd_in + h * g_q;   // hinge: adj qd after integrate^T
-        if constexpr (D::JW_FREE_ROOT != 0) {
+        if constexpr (QRL) {
+            if (lane < 6) g = lane < 3 ? rq_gw : rq_gv;
+        } else if constexpr (D::JW_FREE_ROOT != 0) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
                 const float rk = ex.bcast(r6[k], 0);

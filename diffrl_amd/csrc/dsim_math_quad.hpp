@@ -38,7 +38,10 @@ enum {
     DSIM_QP_XZYW = DSIM_QP(0, 2, 1, 3), DSIM_QP_ZYXW = DSIM_QP(2, 1, 0, 3), DSIM_QP_YXZW = DSIM_QP(1, 0, 2, 3),  // q x e_k
     DSIM_QP_XYZX = DSIM_QP(0, 1, 2, 0), DSIM_QP_WWWX = DSIM_QP(3, 3, 3, 0),   // Hamilton product
     DSIM_QP_YZXY = DSIM_QP(1, 2, 0, 1), DSIM_QP_ZXYY = DSIM_QP(2, 0, 1, 1),
-    DSIM_QP_ZXYZ = DSIM_QP(2, 0, 1, 2), DSIM_QP_YZXZ = DSIM_QP(1, 2, 0, 2)
+    DSIM_QP_ZXYZ = DSIM_QP(2, 0, 1, 2), DSIM_QP_YZXZ = DSIM_QP(1, 2, 0, 2),
+    DSIM_QP_YXWZ = DSIM_QP(1, 0, 3, 2), DSIM_QP_ZWXY = DSIM_QP(2, 3, 0, 1),   // the two pair swaps of a four-term sum
+    DSIM_QP_XYZY = DSIM_QP(0, 1, 2, 1), DSIM_QP_WWWY = DSIM_QP(3, 3, 3, 1),   // dq_qmul_v_int: scalar part in the order y, x, z
+    DSIM_QP_YZXX = DSIM_QP(1, 2, 0, 0), DSIM_QP_ZXYX = DSIM_QP(2, 0, 1, 0)
 };
 
 // member functions (DSIM_FN is `static inline` on the host)
@@ -80,6 +83,10 @@ struct DsimQuadScalar {
                   __builtin_fmaf(-a.c[2], b.c[2], c.c[2]), __builtin_fmaf(-a.c[3], b.c[3], c.c[3])}};
     }
     DSIM_MFN T sel_w(T a, T b) const { return T{{a.c[0], a.c[1], a.c[2], b.c[3]}}; }   // a's x, y, z with b's w
+    // m ? a : b, m the same for all four components (a value every lane of the quad holds: dq_qdot)
+    DSIM_MFN T sel(bool m, T a, T b) const { return m ? a : b; }
+    // a value that is the same in all four components, as one float
+    DSIM_MFN float any(T a) const { return a.c[0]; }
     // components [0, N) from p[0 .. N); the others are 0
     template <int N> DSIM_MFN T ld(const float* p) const {
         T a{{0.f, 0.f, 0.f, 0.f}};
@@ -152,6 +159,8 @@ template <class Exec> struct DsimQuadLanes {
     DSIM_MFN T fma(T a, T b, T cc) const { return __builtin_fmaf(a, b, cc); }
     DSIM_MFN T nfma(T a, T b, T cc) const { return __builtin_fmaf(-a, b, cc); }
     DSIM_MFN T sel_w(T a, T b) const { return c == 3 ? b : a; }
+    DSIM_MFN T sel(bool m, T a, T b) const { return m ? a : b; }
+    DSIM_MFN float any(T a) const { return a; }
     // lanes past the vector's last component re-read it: every address stays inside the vector
     template <int N> DSIM_MFN T ld(const float* p) const { return p[c < N ? c : N - 1]; }
     template <int N> DSIM_MFN void st(float* p, T a) const { p[c] = a; }
@@ -389,6 +398,95 @@ template <class B> DSIM_FN typename B::T dq_qmul_v(const B& b, typename B::T a, 
     r = b.fma(b.mul(b.template perm<DSIM_QP_YZXY>(a), b.qs()), b.template perm<DSIM_QP_ZXYY>(x), r);
     return b.nfma(b.template perm<DSIM_QP_ZXYZ>(a), b.template perm<DSIM_QP_YZXZ>(x), r);
 }
+// ---- the free root's integrator and its adjoint (dsim_core.hpp: dsim_fwd_dynamics_wave, dsim_bwd_joint_wave) --------------------
+// a . x of two quaternions, the same bits in all four components: the pair sums (x + y, z + w) first, then their sum -- an add
+// is commutative, so (x + y) + (z + w) and (z + w) + (x + y) are one value
+template <class B> DSIM_FN typename B::T dq_qdot(const B& b, typename B::T a, typename B::T x) {
+    const typename B::T p = b.mul(a, x);
+    const typename B::T s = b.add(p, b.template perm<DSIM_QP_YXWZ>(p));
+    return b.add(s, b.template perm<DSIM_QP_ZWXY>(s));
+}
+// cotangent of the FIRST operand of a Hamilton product c = a (x) x for the cotangent g of c (dsim_math.hpp: qmul_adj_a):
+// g (x) conj(x), conj's signs folded into the terms
+template <class B> DSIM_FN typename B::T dq_qmul_adj_a(const B& b, typename B::T x, typename B::T g) {
+    typename B::T r = b.mul(b.template perm<DSIM_QP_XYZX>(g), b.template perm<DSIM_QP_WWWX>(x));
+    r = b.nfma(b.mul(b.template perm<DSIM_QP_WWWW>(g), b.qs()), x, r);
+    r = b.nfma(b.mul(b.template perm<DSIM_QP_YZXY>(g), b.qs()), b.template perm<DSIM_QP_ZXYY>(x), r);
+    return b.fma(b.template perm<DSIM_QP_ZXYZ>(g), b.template perm<DSIM_QP_YZXZ>(x), r);
+}
+// the identity quaternion (0, 0, 0, 1) from the sign constant (1, 1, 1, -1): 1/2 - qs / 2, exact
+template <class B> DSIM_FN typename B::T dq_qident(const B& b) { return b.nfma(b.qs(), b.spl(0.5f), b.spl(0.5f)); }
+// loads and stores of a 3-vector / quaternion by per-lane address (the quad backend's w lane stores nothing of a 3-vector)
+template <class B> DSIM_FN typename B::T dq_ld3(const B& b, const float* p) { return b.template ld<3>(p); }
+template <class B> DSIM_FN typename B::T dq_ldq(const B& b, const float* p) { return b.template ld<4>(p); }
+template <class B> DSIM_FN void dq_st3(const B& b, float* p, typename B::T a) {
+    if (b.xyz()) b.template st<3>(p, a);
+}
+template <class B> DSIM_FN void dq_stq(const B& b, float* p, typename B::T a) { b.template st<4>(p, a); }
+// Semi-implicit Euler of a free joint (sim.py:1505-1636): w = qd_w + a_w h, vn = qd_v + a_v h, pn = p + (vn + w x p) h,
+// rt = r + (w, 0) (x) r h / 2, rn = rt / |rt| -- the identity quaternion where |rt|^2 is below the smallest normal (il == 0;
+// dsim_math.hpp: dsim_inv_len).  il rides in the checkpoint for integrate^T (dsim_core.hpp: DsimSavedIl).  The test on il is a
+// select: all four lanes of a quad execute every permutation.
+// The integrator keeps the roundings of its one-joint-per-lane form (dsim_math.hpp structs, as the compiler contracted them): the
+// state after a step is the quantity a rollout feeds back 512 times, and environments that sit at a contact or joint-limit
+// threshold follow another branch after a change in its last bit (tests/test_reference_episodes.py counts them).  Three places
+// differ from the general forms above:
+//   dq_qmul_v_int   the scalar part of (a, 0) (x) x summed in the order y, x, z (-(a_y x_y) rounded, the other two fused)
+//   dq_qnorm2_int   |a|^2 as one chain y^2, + x^2, + z^2, + w^2 (four broadcasts) instead of the pair sums of dq_qdot
+//   w x p           as -(p x w) through dq_cross_sub: the product that is rounded on its own is the second one
+template <class B> DSIM_FN typename B::T dq_qmul_v_int(const B& b, typename B::T a, typename B::T x) {
+    typename B::T r = b.mul(b.mul(b.template perm<DSIM_QP_XYZY>(a), b.qs()), b.template perm<DSIM_QP_WWWY>(x));
+    r = b.fma(b.mul(b.template perm<DSIM_QP_YZXX>(a), b.qs()), b.template perm<DSIM_QP_ZXYX>(x), r);
+    return b.nfma(b.template perm<DSIM_QP_ZXYZ>(a), b.template perm<DSIM_QP_YZXZ>(x), r);
+}
+template <class B> DSIM_FN typename B::T dq_qnorm2_int(const B& b, typename B::T a) {
+    const typename B::T ax = b.template perm<DSIM_QP_XXXX>(a), ay = b.template perm<DSIM_QP_YYYY>(a);
+    const typename B::T az = b.template perm<DSIM_QP_ZZZZ>(a), aw = b.template perm<DSIM_QP_WWWW>(a);
+    return b.fma(aw, aw, b.fma(az, az, b.fma(ax, ax, b.mul(ay, ay))));
+}
+// (rt from r and w = qd_w + qdd_w h, and 1 / |rt|: integrate^T repeats the integrator's own expressions, rounding included)
+template <class B> DSIM_FN typename B::T dq_root_rt(const B& b, typename B::T r, typename B::T w, float h) {
+    return dq_axpy(b, dq_scale(b, dq_qmul_v_int(b, w, r), 0.5f), h, r);
+}
+template <class B> DSIM_FN float dq_root_il(const B& b, typename B::T rt) { return dsim_inv_len(b.any(dq_qnorm2_int(b, rt))); }
+template <class B> struct DsimQuadRootStep {
+    typename B::T pn, rn, w, vn;
+    float il;
+};
+template <class B>
+DSIM_FN DsimQuadRootStep<B> dq_root_integrate(const B& b, typename B::T p, typename B::T r, typename B::T qd_w, typename B::T qd_v,
+                                              typename B::T a_w, typename B::T a_v, float h) {
+    typedef typename B::T T;
+    DsimQuadRootStep<B> o;
+    o.w = dq_axpy(b, a_w, h, qd_w);
+    o.vn = dq_axpy(b, a_v, h, qd_v);
+    o.pn = dq_axpy(b, dq_cross_sub(b, o.vn, p, o.w), h, p);
+    const T rt = dq_root_rt(b, r, o.w, h);
+    o.il = dq_root_il(b, rt);
+    o.rn = b.sel(o.il > 0.0f, dq_scale(b, rt, o.il), dq_qident(b));
+    return o;
+}
+// integrate^T of the same update: cotangents g_pn, g_rn of the new pose and gqd_w, gqd_v of the new twist in; aq_p, aq_r: the
+// cotangent of the old pose, g_w, g_v: that of the twist (w, vn).  il: the integrator's (0: the normalisation passed nothing)
+template <class B> struct DsimQuadRootAdj {
+    typename B::T aq_p, aq_r, g_w, g_v;
+};
+template <class B>
+DSIM_FN DsimQuadRootAdj<B> dq_root_integrate_adj(const B& b, typename B::T p, typename B::T r, typename B::T w, typename B::T rt, float il,
+                                                 typename B::T g_pn, typename B::T g_rn, typename B::T gqd_w, typename B::T gqd_v, float h) {
+    typedef typename B::T T;
+    DsimQuadRootAdj<B> o;
+    const T rn = dq_scale(b, rt, il);
+    const T g_rt = b.sel(il > 0.0f, dq_scale(b, b.nfma(rn, dq_qdot(b, rn, g_rn), g_rn), il), b.spl(0.f));
+    const float hh = 0.5f * h;
+    o.aq_r = b.nfma(dq_qmul_v(b, w, g_rt), b.spl(hh), g_rt);   // g_rt + conj(W) (x) g_rt h / 2, W = (w, 0)
+    const T g_dp = dq_scale(b, g_pn, h);
+    o.g_w = dq_cross_acc(b, dq_axpy(b, dq_qmul_adj_a(b, r, g_rt), hh, gqd_w), p, g_dp);
+    o.g_v = b.add(g_dp, gqd_v);
+    o.aq_p = dq_cross_sub(b, g_pn, w, g_dp);
+    return o;
+}
+
 // Cotangent of a spatial inertia's 10 parameters (dsim_math.hpp: g[10]; the mass word is never needed).  The six words of the
 // symmetric block are held as the three rows of G + G^T, G the cotangent of A's nine entries: the off-diagonal entries are the
 // words themselves, the diagonal carries TWICE its word -- which is the matrix the pose wrench wants (dsim_core.hpp:
