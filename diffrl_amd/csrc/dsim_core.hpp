@@ -2346,6 +2346,75 @@ template <class Ctx, class Exec> struct DsimQuadRoot {
         else return false;
     }();
 };
+// ---- launch-invariant operands of the joint-space phases in registers; H^-1 x by row broadcast --------------------------------
+// Both joint-space phases (dsim_fwd_dynamics_wave, dsim_bwd_joint_wave) reloaded, in every substep and behind per-lane addresses,
+// operands that do not change from substep to substep: the dof lane's row of H^-1 (14 words; it changes at a mass-matrix refresh
+// only) and the joint constants lower, upper, target, lke, tke, tkd, lkd with the forward's act (they do not change within a
+// launch).  An executor with a jregs() block keeps them per lane across the substeps:
+//   * forward: the constants and act are loaded once, in front of the substep loop (dsim_joint_regs_begin); hrow in every refresh
+//     substep, behind the Gauss-Jordan that has just rewritten WF(hinv) -- the first substep of a launch is one.
+//   * adjoint: hrow is loaded when h_ok is false; h_ok is cleared BEHIND the substep that ends a group (update_mass: the next
+//     substep's inverse is another group's, wherever it is brought in from).  The constants are loaded once, while c_ok is false.
+//     Every launch starts with both flags false.  Nothing inside a launch writes the constants after the prologue.
+// Same words, same operations: no rounding changes.  Executors without the block (the host harness) and the kernels whose register
+// budget has no room for 22 more VGPRs (the lean adjoints at 240 .. 245, the two-environment forwards at 218 .. 231) reload.
+struct DsimJointRegs {
+    float hrow[DSIM_JW_ND_MAX];
+    float lower, upper, target, lke, tke, tkd, lkd, act;
+    bool h_ok = false, c_ok = false;
+};
+template <class Exec, class = void> struct DsimHasJointRegs : std::false_type {};
+template <class Exec> struct DsimHasJointRegs<Exec, std::void_t<decltype(std::declval<Exec&>().jregs(0))>> : std::true_type {};
+// ... and an executor with row_matvec() (one environment per wavefront) forms H^-1 x with the broadcast on the multiply-add's
+// operand; the others keep the v_readlane / crossbar loop.  Same terms in the same order, each a fused multiply-add.
+template <class Exec, class = void> struct DsimHasRowBcast : std::false_type {};
+template <class Exec> struct DsimHasRowBcast<Exec, std::enable_if_t<Exec::ROW_BCAST>> : std::true_type {};
+template <class Ctx, class Exec> struct DsimRowMatvec {
+    static constexpr bool value = []() {
+        if constexpr (DsimHasRowBcast<Exec>::value && DsimQuadRoot<Ctx, Exec>::QUAD) return decltype(Ctx::d)::nd <= 16;
+        else return false;
+    }();
+};
+template <class Ctx, class Exec> struct DsimJointRegsFwd {
+    static constexpr bool value = DsimHasJointRegs<Exec>::value && DsimRowMatvec<Ctx, Exec>::value;
+};
+template <class Ctx, class Exec> struct DsimJointRegsBwd {
+    static constexpr bool value = DsimHasJointRegs<Exec>::value && DsimRowMatvec<Ctx, Exec>::value && !Ctx::LEAN;
+};
+// DPP_NEXT: the result's next use may be a DPP operand (the forward hands qdd to the link lanes by a row shift).
+// PRECONDITION of the row-broadcast form: called with every lane of the wave enabled (both callers sit at the top level of an
+// Exec::run block of the main wave, behind the reconvergence of the hinge branch); a source lane that EXEC disables is not read.
+template <int ND, class Ctx, bool DPP_NEXT, class Exec> DSIM_FN float dsim_joint_matvec(Exec& ex, const float* hrow, float x) {
+    if constexpr (DsimRowMatvec<Ctx, Exec>::value) {
+        static_assert(ND <= 16, "row broadcast: the model's dofs lie in one 16-lane row (dof lane = dof index)");
+        return ex.template row_matvec<ND, DPP_NEXT>(hrow, x);
+    } else {
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < ND; ++j) acc += hrow[j] * ex.bcast(x, j);
+        return acc;
+    }
+}
+// The forward launches call this once, behind the phase that brings act in and in front of the substep loop: the joint constants
+// and act of the dof lanes.  The row of H^-1 follows in the first substep, which refreshes the mass matrix in every launch
+// (s % mm_freq == 0 at s = 0).  Flags inside the loop instead (as the adjoint has them) cost the forward kernels more SGPR spill
+// traffic than the loads they saved.
+template <class Ctx, class Exec> DSIM_FN void dsim_joint_regs_begin(const Ctx& c, Exec& ex) {
+    if constexpr (DsimJointRegsFwd<Ctx, Exec>::value) {
+        using D = decltype(c.d);
+        ex.run([&](int lane) {
+            const DsimTopoRegs& tp = ex.topo(lane);
+            int dtype = tp.dof_type;
+            DSIM_OPAQUE(dtype);
+            const int di = tp.dof_link, d = lane < D::nd ? lane : 0;
+            const int qi = (dtype == DSIM_JOINT_PRISMATIC || dtype == DSIM_JOINT_REVOLUTE) ? tp.dof_cs : 0;
+            DsimJointRegs& jr = ex.jregs(lane);
+            jr.act = WF(act)[d];
+            jr.lower = CF(lower)[qi]; jr.upper = CF(upper)[qi]; jr.target = CF(target)[qi];
+            jr.lke = CF(lke)[di]; jr.tke = CF(tke)[di]; jr.tkd = CF(tkd)[di]; jr.lkd = CF(lkd)[di];
+        });
+    }
+}
 template <class Ctx, class Exec>
 DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float* g_hinv, bool update_mass) {
     ex.mark(3);
@@ -2376,12 +2445,29 @@ DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float*
         const bool hinge = dtype == DSIM_JOINT_PRISMATIC || dtype == DSIM_JOINT_REVOLUTE;
         const int qi = hinge ? dcs : (dtype == DSIM_JOINT_BALL ? dcs + (d - dds) : 0);
         const sv6 Sd = ldsv(WF(S) + 6 * d);
-        const float q_d = WF(q)[qi], qd_d = WF(qd)[d], act_d = WF(act)[d];
-        const float lower = CF(lower)[qi], upper = CF(upper)[qi], target = CF(target)[qi];
-        const float lke = CF(lke)[di], tke = CF(tke)[di], tkd = CF(tkd)[di], lkd = CF(lkd)[di];
-        float hrow[nd];
+        const float q_d = WF(q)[qi], qd_d = WF(qd)[d];
+        float act_d, lower, upper, target, lke, tke, tkd, lkd;
+        float hrow_l[nd];
+        const float* hrow = hrow_l;
+        if constexpr (DsimJointRegsFwd<Ctx, Exec>::value) {
+            // launch-invariant operands stay in the executor's registers (DsimJointRegs): the constants and act from the launch's
+            // first substep on, the row of H^-1 from each refresh on (the Gauss-Jordan in front of this phase has just rewritten it)
+            // (no flags here: dsim_joint_regs_begin has run, and the launch's first substep is a refresh substep)
+            DsimJointRegs& jr = ex.jregs(lane);
+            if (update_mass) {
 #pragma unroll
-        for (int j = 0; j < nd; ++j) hrow[j] = WF(hinv)[d * nd + j];
+                for (int j = 0; j < nd; ++j) jr.hrow[j] = WF(hinv)[d * nd + j];
+            }
+            act_d = jr.act; lower = jr.lower; upper = jr.upper; target = jr.target;
+            lke = jr.lke; tke = jr.tke; tkd = jr.tkd; lkd = jr.lkd;
+            hrow = jr.hrow;
+        } else {
+            act_d = WF(act)[d];
+            lower = CF(lower)[qi]; upper = CF(upper)[qi]; target = CF(target)[qi];
+            lke = CF(lke)[di]; tke = CF(tke)[di]; tkd = CF(tkd)[di]; lkd = CF(lkd)[di];
+#pragma unroll
+            for (int j = 0; j < nd; ++j) hrow_l[j] = WF(hinv)[d * nd + j];
+        }
         // link role
         int ltype = tp.own_type;
         DSIM_OPAQUE(ltype);
@@ -2442,10 +2528,8 @@ DSIM_FN void dsim_fwd_dynamics_wave(const Ctx& c, Exec& ex, float* g_row, float*
         } else if (dtype == DSIM_JOINT_BALL) {
             t = t - qd_d * tkd - q_d * tke;
         }
-        // ---- qdd = H^-1 tau: tau_j travels by v_readlane
-        float acc = 0.f;
-#pragma unroll
-        for (int j = 0; j < nd; ++j) acc += hrow[j] * ex.bcast(t, j);
+        // ---- qdd = H^-1 tau: tau_j travels by v_readlane (DsimRowMatvec: by row broadcast on the multiply-add's operand)
+        const float acc = dsim_joint_matvec<nd, Ctx, true>(ex, hrow, t);
         if (is_dof) {
             WF(tau)[lane] = t;
             WF(qdd)[lane] = acc;
@@ -2755,7 +2839,10 @@ template <class Ctx, class Exec> DSIM_FN void dsim_check_unit_quats(const Ctx& c
     }
 }
 
-// one substep on the LDS-resident state; g_row / g_hinv: where to stream the saved block / the fresh inverse (or null)
+// one substep on the LDS-resident state; g_row / g_hinv: where to stream the saved block / the fresh inverse (or null).
+// A caller whose kernel takes DsimJointRegsFwd must have called dsim_joint_regs_begin behind the phase that stores act, and its
+// first substep must be a refresh substep (update_mass): the forward keeps no validity flags (the block's h_ok / c_ok are the
+// adjoint's), so a substep without both reads registers nobody loaded.  dsim_sim_step_forward and the env forward comply.
 template <class Ctx, class Exec>
 DSIM_FN void dsim_fwd_substep(const Ctx& c, Exec& ex, bool update_mass, float* g_row = nullptr, float* g_hinv = nullptr) {
     constexpr bool wide = DsimWideOverlap<Ctx, Exec>::value;
@@ -2823,6 +2910,7 @@ DSIM_FN void dsim_sim_step_forward(const Ctx& c, Exec& ex, int substeps, int mm_
         for (int k = lane; k < M; k += Exec::NL) WF(mact)[k] = g_mact[k];
     });
     dsim_check_unit_quats(c, ex, g_status, env);
+    dsim_joint_regs_begin(c, ex);
     for (int s = 0; s < substeps; ++s)
         dsim_fwd_substep(c, ex, (s % mm_freq) == 0, g_ckpt ? g_ckpt + (size_t)s * dsim_row(c) : nullptr,
                          g_ckpt ? dsim_ckpt_hinv(c, g_ckpt, substeps, s / mm_freq) : nullptr);
@@ -3307,7 +3395,7 @@ template <class Ctx, class Exec> struct DsimJointWave {
         }
     }();
 };
-template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_wave(const Ctx& c, Exec& ex) {
+template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_wave(const Ctx& c, Exec& ex, [[maybe_unused]] bool update_mass) {
     using D = decltype(c.d);
     constexpr int nd = D::nd;
     ex.run([&](int lane) {
@@ -3321,13 +3409,35 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_wave(const Ctx& c, 
         const int i = tp.dof_link, cs = tp.dof_cs, d = is_dof ? lane : 0;
         const bool hinge = type == DSIM_JOINT_PRISMATIC || type == DSIM_JOINT_REVOLUTE;
         const int qi = hinge ? cs : 0;
-        float hrow[nd];
+        float hrow_l[nd];
+        const float* hrow = hrow_l;
+        float tke, tkd, lke, lkd, lower, upper;
+        if constexpr (DsimJointRegsBwd<Ctx, Exec>::value) {
+            // launch-invariant operands stay in the executor's registers (DsimJointRegs): the constants from the launch's first
+            // substep on, the row of H^-1 for a whole group of substeps (h_ok is cleared below, behind the group's last one)
+            DsimJointRegs& jr = ex.jregs(lane);
+            if (!jr.h_ok) {
 #pragma unroll
-        for (int j = 0; j < nd; ++j) hrow[j] = WF(hinv)[d * nd + j];
+                for (int j = 0; j < nd; ++j) jr.hrow[j] = WF(hinv)[d * nd + j];
+            }
+            if (!jr.c_ok) {
+                jr.tke = CF(tke)[i]; jr.tkd = CF(tkd)[i]; jr.lke = CF(lke)[i]; jr.lkd = CF(lkd)[i];
+                jr.lower = CF(lower)[qi]; jr.upper = CF(upper)[qi];
+                jr.c_ok = true;
+            }
+            jr.h_ok = !update_mass;
+            tke = jr.tke; tkd = jr.tkd; lke = jr.lke; lkd = jr.lkd; lower = jr.lower; upper = jr.upper;
+            hrow = jr.hrow;
+        } else {
+#pragma unroll
+            for (int j = 0; j < nd; ++j) hrow_l[j] = WF(hinv)[d * nd + j];
+        }
         const sv6 ft = ldsv(WF(ftot) + 6 * i);
         const float q = WF(q)[qi];
-        const float tke = CF(tke)[i], tkd = CF(tkd)[i], lke = CF(lke)[i], lkd = CF(lkd)[i];
-        const float lower = CF(lower)[qi], upper = CF(upper)[qi];
+        if constexpr (!DsimJointRegsBwd<Ctx, Exec>::value) {
+            tke = CF(tke)[i]; tkd = CF(tkd)[i]; lke = CF(lke)[i]; lkd = CF(lkd)[i];
+            lower = CF(lower)[qi]; upper = CF(upper)[qi];
+        }
         const float g_q = WF(aq)[qi], g_qd_in = WF(aqd)[d], g_act = WF(aact)[d];
         // ---- integrate^T: the free root on lane 0 (its six new adj qd values in r6), a hinge on its dof lane
         float r6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -3418,10 +3528,8 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_wave(const Ctx& c, 
             }
         }
         const float aqdd = h * g;
-        // ---- adj tau = H^-1 adj qdd (hinv is symmetric): adj qdd_j travels by v_readlane
-        float at = 0.f;
-#pragma unroll
-        for (int j = 0; j < nd; ++j) at += hrow[j] * ex.bcast(aqdd, j);
+        // ---- adj tau = H^-1 adj qdd (hinv is symmetric): adj qdd_j travels by v_readlane (DsimRowMatvec: by row broadcast)
+        const float at = dsim_joint_matvec<nd, Ctx, false>(ex, hrow, aqdd);
         // ---- per-dof cotangents of tau
         if (is_dof) {
             WF(atau)[lane] = at;
@@ -3446,7 +3554,7 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_joint_space(const Ctx& c,
     ex.mark(7);
     const int nd = c.d.nd;
     constexpr bool joint_wave = DsimJointWave<Ctx, Exec>::value;
-    if constexpr (joint_wave) dsim_bwd_joint_wave(c, ex);
+    if constexpr (joint_wave) dsim_bwd_joint_wave(c, ex, update_mass);
     // integrate^T per link: loads, arithmetic, stores (aq / aqd alias aqn / aqdn: every lane replaces its own link's words)
     if constexpr (!joint_wave) ex.run([&](int lane) {
         constexpr int MASK = dsim_tmask_static<Ctx>();
@@ -5225,6 +5333,7 @@ DSIM_FN void dsim_env_fused_forward(const Ctx& c, Exec& ex, const DsimEnvSpec& s
     });
     dsim_env_load_actions(c, ex, sp, g_actions, true);
     dsim_check_unit_quats(c, ex, g_status, e);
+    dsim_joint_regs_begin(c, ex);
     for (int s = 0; s < substeps; ++s)
         dsim_fwd_substep(c, ex, (s % mm_freq) == 0, g_ckpt ? g_ckpt + (size_t)s * dsim_row(c) : nullptr,
                          g_ckpt ? dsim_ckpt_hinv(c, g_ckpt, substeps, s / mm_freq) : nullptr);

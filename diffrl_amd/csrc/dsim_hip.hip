@@ -561,6 +561,81 @@ template <int NW, int PF = 6, int CW = 0, bool HELPER = false, int EPW = 1> stru
     // per-lane topology records (dsim_core.hpp: DsimTopoRegs, dsim_topo_init)
     DsimTopoRegs topo_;
     __device__ __forceinline__ DsimTopoRegs& topo(int) { return topo_; }
+    // per-lane copies of what the joint-space phases would otherwise reload from LDS in every substep (dsim_core.hpp:
+    // DsimJointRegs, DsimJointRegsFwd / DsimJointRegsBwd): the dof lane's row of H^-1 and its joint constants.  The flags start
+    // false in every launch; kernels whose traits are off never touch the block and it costs them nothing.
+    DsimJointRegs jregs_;
+    __device__ __forceinline__ DsimJointRegs& jregs(int) { return jregs_; }
+    // acc = fma(h[j], x of lane j of this lane's 16-lane ROW, acc) for j = 0 .. N - 1, from acc = 0: the mat-vec of the joint-space
+    // phases (dof j on lane j, N <= 16: one row) as N v_fmac_f32 with the broadcast ON THE OPERAND (row_newbcast:j) instead of N
+    // v_readlane + v_fmac pairs -- same terms, same order, same fused multiply-add.  x may have been written right before: the
+    // s_nop covers the two wait states between a VALU write and a DPP read (as in add_from_above); the accumulator is not read
+    // through DPP.  PRECONDITION: every lane of the wave is enabled in EXEC (uniform control flow, as inside Exec::run of the main
+    // wave): unlike v_readlane, a DPP operand whose source lane is disabled is not read (bound_ctrl off: the term's write is
+    // dropped), so a caller inside a divergent region would get other values than the v_readlane loop.  One environment per
+    // wavefront only (the pair kernels keep the crossbar).
+    // Pinned on hardware by tools/micro/dpp_semantics.hip (profiles/joint_regs_ab.txt has its output).
+    static constexpr bool ROW_BCAST = EPW == 1;
+    // ONE asm statement for the whole chain: the compiler puts an s_nop behind every inline-assembly statement, which a statement
+    // per term would pay N times.  DSIM_RB_n is the chain of n terms; operand 2 + j is h[j] (h[N - 1] again beyond the model's N).
+    // DPP_NEXT: the caller's next use of the result may be a DPP operand (the forward's row shift of qdd to the link lanes).  The
+    // compiler's hazard recogniser does not see a VGPR written inside inline assembly, so the two wait states are placed here.
+#define DSIM_RB_T(j, op) "v_fmac_f32_dpp %0, %1, %" #op " row_newbcast:" #j " row_mask:0xf bank_mask:0xf\n\t"
+#define DSIM_RB_1 DSIM_RB_T(0, 2)
+#define DSIM_RB_2 DSIM_RB_1 DSIM_RB_T(1, 3)
+#define DSIM_RB_3 DSIM_RB_2 DSIM_RB_T(2, 4)
+#define DSIM_RB_4 DSIM_RB_3 DSIM_RB_T(3, 5)
+#define DSIM_RB_5 DSIM_RB_4 DSIM_RB_T(4, 6)
+#define DSIM_RB_6 DSIM_RB_5 DSIM_RB_T(5, 7)
+#define DSIM_RB_7 DSIM_RB_6 DSIM_RB_T(6, 8)
+#define DSIM_RB_8 DSIM_RB_7 DSIM_RB_T(7, 9)
+#define DSIM_RB_9 DSIM_RB_8 DSIM_RB_T(8, 10)
+#define DSIM_RB_10 DSIM_RB_9 DSIM_RB_T(9, 11)
+#define DSIM_RB_11 DSIM_RB_10 DSIM_RB_T(10, 12)
+#define DSIM_RB_12 DSIM_RB_11 DSIM_RB_T(11, 13)
+#define DSIM_RB_13 DSIM_RB_12 DSIM_RB_T(12, 14)
+#define DSIM_RB_14 DSIM_RB_13 DSIM_RB_T(13, 15)
+#define DSIM_RB_15 DSIM_RB_14 DSIM_RB_T(14, 16)
+#define DSIM_RB_16 DSIM_RB_15 DSIM_RB_T(15, 17)
+#define DSIM_RB_H(j) "v"(h[(j) < N ? (j) : N - 1])
+    // (the accumulator is written by the first term while the later terms still read x and h: early clobber, no input shares its register)
+#define DSIM_RB_ASM(n, tail)                                                                                                        \
+    asm volatile("s_nop 1\n\t" DSIM_RB_##n tail : "+&v"(acc) : "v"(x), DSIM_RB_H(0), DSIM_RB_H(1), DSIM_RB_H(2), DSIM_RB_H(3),      \
+                 DSIM_RB_H(4), DSIM_RB_H(5), DSIM_RB_H(6), DSIM_RB_H(7), DSIM_RB_H(8), DSIM_RB_H(9), DSIM_RB_H(10), DSIM_RB_H(11),   \
+                 DSIM_RB_H(12), DSIM_RB_H(13), DSIM_RB_H(14), DSIM_RB_H(15))
+#define DSIM_RB_CASE(n)                                                                                                             \
+    if constexpr (N == n) {                                                                                                         \
+        if constexpr (DPP_NEXT) DSIM_RB_ASM(n, "s_nop 1");                                                                          \
+        else DSIM_RB_ASM(n, "");                                                                                                    \
+    }
+    template <int N, bool DPP_NEXT> __device__ __forceinline__ float row_matvec(const float* h, float x) {
+        static_assert(EPW == 1, "the row broadcast serves one environment per wavefront");
+        static_assert(N >= 1 && N <= 16, "the dofs must lie in one 16-lane row");
+        float acc = 0.f;
+        DSIM_RB_CASE(1) DSIM_RB_CASE(2) DSIM_RB_CASE(3) DSIM_RB_CASE(4) DSIM_RB_CASE(5) DSIM_RB_CASE(6) DSIM_RB_CASE(7) DSIM_RB_CASE(8)
+        DSIM_RB_CASE(9) DSIM_RB_CASE(10) DSIM_RB_CASE(11) DSIM_RB_CASE(12) DSIM_RB_CASE(13) DSIM_RB_CASE(14) DSIM_RB_CASE(15) DSIM_RB_CASE(16)
+        return acc;
+    }
+#undef DSIM_RB_CASE
+#undef DSIM_RB_ASM
+#undef DSIM_RB_H
+#undef DSIM_RB_16
+#undef DSIM_RB_15
+#undef DSIM_RB_14
+#undef DSIM_RB_13
+#undef DSIM_RB_12
+#undef DSIM_RB_11
+#undef DSIM_RB_10
+#undef DSIM_RB_9
+#undef DSIM_RB_8
+#undef DSIM_RB_7
+#undef DSIM_RB_6
+#undef DSIM_RB_5
+#undef DSIM_RB_4
+#undef DSIM_RB_3
+#undef DSIM_RB_2
+#undef DSIM_RB_1
+#undef DSIM_RB_T
     // software prefetch of one checkpoint row: global loads are issued here and stay in flight (registers) until
     // commit() stores them to LDS one adjoint substep later; rows longer than 64*DSIM_PF lanes*regs are read at commit
     // (a native vector type: the may_alias struct dsim_f4 of the copy loops is not promoted to registers -- an array of
