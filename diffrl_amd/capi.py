@@ -121,6 +121,7 @@ ABI = {
     "dsim_model_create": (_int, [C.POINTER(ModelDesc), C.POINTER(_vp)]),
     "dsim_model_destroy": (_int, [_vp]),
     "dsim_model_variant": (_int, [_vp]),
+    "dsim_model_waves": (_int, [_vp]),
     "dsim_model_device": (_int, [_vp]),
     "dsim_ckpt_floats": (C.c_int64, [_vp, _int]),
     "dsim_ckpt_floats_mm": (C.c_int64, [_vp, _int, _int]),

@@ -1905,6 +1905,7 @@ int dsim_mass_matrix_backward(const dsim_model* m, int n_envs, const float* q, c
 
 /* 0 = generic kernels, >0 = index of the specialised variant in use (diagnostics / tests) */
 int dsim_model_variant(const dsim_model* m) { return m ? m->variant : -1; }
+int dsim_model_waves(const dsim_model* m) { return m ? m->waves : -1; }
 int dsim_model_device(const dsim_model* m) { return m ? m->device : -1; }
 
 #ifdef DSIM_STAMPS

@@ -97,6 +97,7 @@ class Engine:
             self._ck(self._lib.dsim_model_set_ckpt_mode(h, capi.CKPT_LEAN if self.ckpt_mode == "lean" else capi.CKPT_FULL))
         assert int(self._lib.dsim_model_device(h)) == self.device.index
         self.variant = int(self._lib.dsim_model_variant(h))  # 0 = generic kernels, > 0 = specialised for this model
+        self.waves = int(self._lib.dsim_model_waves(h))      # wavefronts per environment of its kernels: 1 or 4
         self.n_q, self.n_qd, self.n_muscles = template.n_q, template.n_qd, template.n_muscles
         # joint_q ENTERING the last substep of the most recent forward() with gradients on ([n_envs, n_q], a copy: n_q floats per
         # environment -- never a reference to the checkpoint itself, which is hundreds of MB for the humanoid and must die with

@@ -85,6 +85,20 @@ typedef struct dsim_model_desc {
 
 typedef struct dsim_model dsim_model; /* opaque, owns device copies of the template */
 
+/* Admitted models -- the one statement of the envelope (DESIGN.md "Admitted models" has the reasons; tests/big_models.py
+ * builds a model at every edge of it).  dsim_model_create accepts an articulation with
+ *   1 <= n_links <= 64, 1 <= n_qd <= 64, 1 <= n_q <= 96   (DSIM_ERR_INVALID beyond, "n_links must be in [1,64]" ...; with the
+ *                        five joint kinds 64 dofs reach at most 85 coordinates, so n_q never binds on its own),
+ *   any count of contacts, muscles and way-points whose LDS image of one environment -- constants, forward and adjoint work
+ *                        arrays -- is at most 160 KiB = 163,840 bytes (DSIM_ERR_LIMIT beyond),
+ *   joints of the five kinds above, parents before children, a block-diagonal body_I_m, an unrotated joint_X_cm.
+ * Such a model runs every call below on the generic (run-time layout) kernels, or on a kernel set compiled for it, except:
+ *   dsim_step_backward_literal   n_links <= 24 and n_qd <= 28 (DSIM_ERR_LIMIT beyond; dsim_step_backward has no such limit),
+ *   dsim_step_backward_params    LDS image + 4 * (5 * n_qd + 4 * n_contacts) bytes <= 160 KiB (DSIM_ERR_LIMIT beyond;
+ *                                dsim_step_backward still works),
+ *   dsim_step_backward_multi, dsim_step_jacobian   n_envs * n_cot <= 2^24 - 1 workgroups in one call
+ *                                (DSIM_ERR_LIMIT beyond; dsim_step_jacobian: n_cot = n_q + n_qd). */
+
 const char* dsim_last_error(void);
 int dsim_version(void);
 
@@ -98,6 +112,10 @@ int dsim_model_device(const dsim_model* m);   /* HIP device index the model was 
 /* 0: generic kernels (runtime layout); > 0: a per-model specialised kernel set is in use (layout matched a
  * compile-time table exactly).  Same results either way. */
 int dsim_model_variant(const dsim_model* m);
+/* Wavefronts per environment of this model's kernels: 1, or 4 for a model with more than 64 ground contacts or more than 64
+ * active muscle segments (the generic kernels: DSIM_WAVES=1|4 in the environment at dsim_model_create overrides the choice).
+ * Same results either way. */
+int dsim_model_waves(const dsim_model* m);
 
 /* Floats per environment of the checkpoint the forward launch leaves in HBM for the adjoint launch: per
  * substep one "saved block" (q, qd and the forward intermediates the adjoint reads: transforms, motion
