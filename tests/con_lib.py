@@ -1,64 +1,29 @@
 """Test infrastructure of the differentiable ground-contact read-out (dsim_ground_contacts / dsim_ground_contacts_backward):
 
-* the host harness for this phase code, tests/emu/dsim_emu_con.cpp (a translation unit that includes dsim_emu.cpp), compiled here
-  with the flags of tests/emu/Makefile to tests/emu/libdsim_emu_con.so (and libdsim_emu_con_user.so with the layouts of the two
-  user models) when it is older than its sources, and its entry points;
+* the entry points of the lane-serial host harness for this phase code (tests/emu/dsim_emu_con.cpp; tests/emu_lib.py loads the
+  harness), for the shipped layouts and for the two user models of tests/golden/user_*.npz;
 * a float64 numpy statement of the contact forward (on the frames and twists of kin_lib.fk, or on recorded ones) and of its
   adjoint, chained with kin_lib.fk_adjoint: the reference for `point` and `vel`, which the reference simulator has no tensor
   of, and for models it has no recording of.
 """
 import ctypes as C
-import os
-import re
-import shlex
-import subprocess
 
 import numpy as np
 
 from diffrl_amd.capi import make_desc
-from emu_lib import EMU_DIR, f32, mode, ptr
+from emu_lib import ROOT  # noqa: F401
+from emu_lib import emu, emu_user, f32, mode, ptr
 import kin_lib
 from kin_lib import rot
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENVS = ("ant", "humanoid", "snu", "hopper", "cheetah")   # the models with ground contacts
 EDGE = 1e-4   # |point.y| below which fp32 rounding may flip the active set of a contact
-_libs = {}
-
-
-def _make_var(name):
-    src = open(os.path.join(EMU_DIR, "Makefile")).read().replace("\\\n", " ")
-    return re.search(r"^%s\s*\??=\s*(.*)$" % name, src, re.M).group(1).strip()
-
-
-def _harness(user):
-    """libdsim_emu_con.so / libdsim_emu_con_user.so: rebuilt when older than a source of the harness, loaded once"""
-    name = "libdsim_emu_con_user.so" if user else "libdsim_emu_con.so"
-    if name not in _libs:
-        so = os.path.join(EMU_DIR, name)
-        deps = [os.path.normpath(os.path.join(EMU_DIR, s)) for s in _make_var("SRC").split()] + [os.path.join(EMU_DIR, "dsim_emu_con.cpp")]
-        flags = []
-        if user:
-            hdr = os.path.join(ROOT, "tests", "inject", "dsim_static_layouts_user.hpp")
-            if not os.path.exists(hdr):
-                raise RuntimeError("tests/inject/dsim_static_layouts_user.hpp is missing: __graft_entry__.build() generates it")
-            deps.append(hdr)
-            flags = ['-DDSIM_STATIC_LAYOUTS_FILE="../inject/dsim_static_layouts_user.hpp"',
-                     "-DDSIM_STATIC_VARIANTS(X)=X(UserTree) X(UserRowTree)"]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            cxx = os.environ.get("CXX") or _make_var("CXX")
-            tmp = so + ".%d.tmp" % os.getpid()
-            subprocess.check_call([cxx] + shlex.split(_make_var("CXXFLAGS")) + flags + ["-shared", "-o", tmp, "dsim_emu_con.cpp"],
-                                  cwd=EMU_DIR)
-            os.replace(tmp, so)
-        _libs[name] = C.CDLL(so)
-    return _libs[name]
 
 
 def emu_con_forward(t, q, qd, static=False, waves=1, user=False, want=(True, True, True, True)):
     """-> (point, vel, force, link_wrench); an output not wanted is passed as NULL and returned as None.  The buffers start as
     NaN: what comes back was written."""
-    lib = _harness(user)
+    lib = emu_user() if user else emu()
     desc, keep = make_desc(t)
     q, qd = f32(q), f32(qd)
     N, L, Cn = q.shape[0], t.n_links, t.n_contacts
@@ -71,7 +36,7 @@ def emu_con_forward(t, q, qd, static=False, waves=1, user=False, want=(True, Tru
 
 
 def emu_con_backward(t, q, qd, gpoint, gvel, gforce, glw, static=False, waves=1, user=False):
-    lib = _harness(user)
+    lib = emu_user() if user else emu()
     desc, keep = make_desc(t)
     q, qd, gpoint, gvel, gforce, glw = f32(q), f32(qd), f32(gpoint), f32(gvel), f32(gforce), f32(glw)
     N = q.shape[0]

@@ -24,8 +24,8 @@ import ctypes as C
 import numpy as np
 
 from diffrl_amd.capi import make_desc
-from emu_lib import f32, ptr, emu, emu_user, mode
-from kin_lib import ENVS, USER_MODELS, waves_of  # noqa: F401
+from emu_lib import ENVS, USER_MODELS, waves_of  # noqa: F401
+from emu_lib import f32, ptr, emu, emu_user, mode, step_backward, step_forward
 
 FACTOR, FLOOR, CEIL, EXCLUDE = 10.0, 1e-5, 1e-3, 3e-4
 MAX_EXCLUDED = {"snu": 3}          # pairs (state, gq); every other model: none
@@ -74,24 +74,12 @@ def emu_dyn_backward(t, q, qd, act, mact, gtau, gqdd, gfs, static=False, waves=1
 
 def emu_step_adjoint(t, q, qd, act, mact, h, gqd_out, static=False, waves=1, user=False):
     """dsim_step_backward of ONE substep of length h with a fresh mass matrix on the host harness, gq_out = 0:
-    gq_in = h (d qdd / d q)^T g, gact = h (d qdd / d act)^T g (and gmact likewise) -> (gq_in, gact, gmact | None)"""
+    gq_in = h (d qdd / d q)^T g, gact = h (d qdd / d act)^T g (and gmact likewise) -> (gq_in, gact, gmact | None).  Always the
+    generic one-wave path, whatever `static` and `waves` say: the fixed side of the cross-check."""
     lib = emu_user() if user else emu()
-    desc, keep = make_desc(t)
-    q, qd, act, gqd_out = f32(q), f32(qd), f32(act), f32(gqd_out)
-    N = q.shape[0]
-    m = f32(mact) if (mact is not None and t.n_muscles) else np.zeros((N, 0), np.float32)
-    with mode(lib, static, waves):
-        ck = np.zeros((N, int(lib.dsim_emu_ckpt_floats(C.byref(desc), C.c_int(1), C.c_int(1)))), np.float32)
-        qo, qdo = np.zeros_like(q), np.zeros_like(qd)
-        rc = lib.dsim_emu_step_forward(C.byref(desc), C.c_int(N), ptr(q), ptr(qd), ptr(act), ptr(m), C.c_float(h), C.c_int(1), C.c_int(1),
-                                       ptr(qo), ptr(qdo), ptr(ck))
-        assert rc == 0, rc
-        gq_out = np.zeros_like(q)
-        gq, gqd, ga, gm = np.zeros_like(q), np.zeros_like(qd), np.zeros_like(act), np.zeros_like(m)
-        rc = lib.dsim_emu_step_backward(C.byref(desc), C.c_int(N), ptr(ck), ptr(act), ptr(m), C.c_float(h), C.c_int(1), C.c_int(1),
-                                        ptr(gq_out), ptr(gqd_out), ptr(gq), ptr(gqd), ptr(ga), ptr(gm))
-    assert rc == 0, rc
-    return gq, ga, (gm if t.n_muscles else None)
+    ck = step_forward(t, q, qd, act, mact, h, 1, 1, lib=lib)[2]
+    r = step_backward(t, ck, act, mact, h, 1, 1, np.zeros_like(f32(q)), gqd_out, lib=lib)
+    return r["gq"], r["gact"], r["gmact"]
 
 
 # ---- the fixtures' inputs and the bounds ---------------------------------------------------------------------------------

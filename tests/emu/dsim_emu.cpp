@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <vector>
 
 #define DSIM_FN static inline
@@ -248,6 +249,10 @@ template <int NW, int LANES = DSIM_NL> struct HostExecT {
     }
 };
 typedef HostExecT<1> HostExec;
+
+// DSIM_EMU_EXECUTOR_ONLY: the executor alone, without the entry points below and their instantiations of the phase code (the
+// check programs of tests/quad, which drive the phase code's quad primitives on a HostExec themselves)
+#ifndef DSIM_EMU_EXECUTOR_ONLY
 static int g_lean = 0;   // checkpoint mode of the emu entry points (dsim_model_set_ckpt_mode of the library)
 extern "C" void dsim_emu_set_ckpt_lean(int on) { g_lean = on; }
 static int emu_row(const DsimLayout& lay) { return g_lean ? lay.o.xsc - lay.o.q : lay.o.save_words; }
@@ -303,41 +308,6 @@ int dsim_emu_substep_image(const dsim_model_desc* m, const float* q, const float
     memcpy(image, lds.data(), 4 * lay.o.total_words);
     return 0;
 }
-
-int dsim_emu_step_forward(const dsim_model_desc* m, int n_envs, const float* q_in, const float* qd_in,
-                          const float* act, const float* mact, float dt, int substeps, int mm_freq, float* q_out,
-                          float* qd_out, float* ckpt) {
-    DsimLayout lay;
-    if (!dsim_build_layout(*m, lay).empty()) return -1;
-    const int nq = lay.d.nq, nd = lay.d.nd, M = lay.d.M;
-    HostExec ex;
-    for (int e = 0; e < n_envs; ++e) {
-        std::vector<float> lds;
-        DsimCtx c = emu_ctx(lay, lds, dt / float(substeps));
-        dsim_sim_step_forward(c, ex, substeps, mm_freq, q_in + (size_t)e * nq, qd_in + (size_t)e * nd,
-                              act + (size_t)e * nd, M ? mact + (size_t)e * M : nullptr, q_out + (size_t)e * nq,
-                              qd_out + (size_t)e * nd, ckpt ? ckpt + (size_t)e * dsim_ckpt_words(lay.o.save_words, nq, nd, substeps, mm_freq) : nullptr);
-    }
-    return 0;
-}
-}
-
-extern "C" int dsim_emu_step_backward(const dsim_model_desc* m, int n_envs, const float* ckpt, const float* act,
-                                      const float* mact, float dt, int substeps, int mm_freq, const float* gq_out,
-                                      const float* gqd_out, float* gq_in, float* gqd_in, float* gact, float* gmact) {
-    DsimLayout lay;
-    if (!dsim_build_layout(*m, lay).empty()) return -1;
-    const int nq = lay.d.nq, nd = lay.d.nd, M = lay.d.M;
-    HostExec ex;
-    for (int e = 0; e < n_envs; ++e) {
-        std::vector<float> lds;
-        DsimCtx c = emu_ctx(lay, lds, dt / float(substeps));
-        dsim_sim_step_backward(c, ex, substeps, mm_freq, ckpt + (size_t)e * dsim_ckpt_words(lay.o.save_words, nq, nd, substeps, mm_freq), act + (size_t)e * nd,
-                               M ? mact + (size_t)e * M : nullptr, gq_out + (size_t)e * nq, gqd_out + (size_t)e * nd,
-                               gq_in + (size_t)e * nq, gqd_in + (size_t)e * nd, gact ? gact + (size_t)e * nd : nullptr,
-                               (gmact && M) ? gmact + (size_t)e * M : nullptr);
-    }
-    return 0;
 }
 
 // dsim_step_backward_literal on the host: the adjoint phases with the export of (gq_1, gqd_1, adj H), then the forward-mode
@@ -444,6 +414,67 @@ template <bool CKPT_MODES = true, class F> static int emu_each_env(const DsimLay
     });
 }
 
+// ---- the step: forward and adjoint sweep, one environment after the other ----
+// `params`: NULL, or six pointers in the order of the DSIM_PARAM_* fields of include/dsim.h (target_ke, target_kd, limit_ke,
+// limit_kd, target, contact_material), each NULL or an array that replaces the template's in the constant block -- the host form
+// of dsim_model_set_params, a copy into the block at the field's layout offset.
+static void par_apply(DsimLayout& lay, const float* const* params) {
+    if (!params) return;
+    const DsimOff& o = lay.o;
+    const DsimDims& d = lay.d;
+    const int off[6] = {o.tke, o.tkd, o.lke, o.lkd, o.target, o.cmat};
+    const int n[6] = {d.L, d.L, d.L, d.L, d.nq, 4 * d.C};
+    for (int f = 0; f < 6; ++f)
+        if (params[f] && n[f] > 0) memcpy(lay.cblob.data() + off[f], params[f], sizeof(float) * (size_t)n[f]);
+}
+
+extern "C" int dsim_emu_step_forward(const dsim_model_desc* m, const float* const* params, int n_envs, const float* q_in,
+                                     const float* qd_in, const float* act, const float* mact, float dt, int substeps, int mm_freq,
+                                     float* q_out, float* qd_out, float* ckpt) {   // ckpt: null = no checkpoints
+    DsimLayout lay;
+    if (!dsim_build_layout(*m, lay).empty()) return -1;
+    par_apply(lay, params);
+    const size_t nq = lay.d.nq, nd = lay.d.nd, M = lay.d.M;
+    const size_t stride = dsim_ckpt_words(emu_row(lay), lay.d.nq, lay.d.nd, substeps, mm_freq);
+    return emu_each_env(lay, n_envs, dt / float(substeps), [&](auto& c, auto& ex, int e) {
+        dsim_sim_step_forward(c, ex, substeps, mm_freq, q_in + e * nq, qd_in + e * nd, act + e * nd, M ? mact + e * M : nullptr,
+                              q_out + e * nq, qd_out + e * nd, ckpt ? ckpt + e * stride : nullptr);
+    });
+}
+
+// g_dof [n_envs][5][nd], g_contact [n_envs][C][4]: the model-parameter gradients (dsim_core.hpp: DsimParCtxT around
+// dsim_sim_step_backward; the device form is dsim_bwd_param_kernel).  With BOTH null the sweep runs on the plain context:
+// dsim_step_backward itself, the pointer arithmetic of dsim_bwd_kernel.
+extern "C" int dsim_emu_step_backward(const dsim_model_desc* m, const float* const* params, int n_envs, const float* ckpt,
+                                      const float* act, const float* mact, float dt, int substeps, int mm_freq, const float* gq_out,
+                                      const float* gqd_out, float* gq_in, float* gqd_in, float* gact, float* gmact, float* g_dof,
+                                      float* g_contact) {
+    DsimLayout lay;
+    if (!dsim_build_layout(*m, lay).empty()) return -1;
+    par_apply(lay, params);
+    const size_t nq = lay.d.nq, nd = lay.d.nd, M = lay.d.M, C = lay.d.C;
+    const size_t stride = dsim_ckpt_words(emu_row(lay), lay.d.nq, lay.d.nd, substeps, mm_freq);
+    const bool with_params = g_dof || g_contact;
+    std::vector<float> acc;
+    return emu_each_env(lay, n_envs, dt / float(substeps), [&](auto& c0, auto& ex, int e) {
+        auto sweep = [&](auto& c) {
+            dsim_sim_step_backward(c, ex, substeps, mm_freq, ckpt + e * stride, act + e * nd, M ? mact + e * M : nullptr,
+                                   gq_out + e * nq, gqd_out + e * nd, gq_in + e * nq, gqd_in + e * nd, gact ? gact + e * nd : nullptr,
+                                   (gmact && M) ? gmact + e * M : nullptr);
+        };
+        if (!with_params) return sweep(c0);
+        using Base = std::decay_t<decltype(c0)>;
+        DsimParCtxT<decltype(c0.o), decltype(c0.d), Base::LEAN> c;
+        static_cast<Base&>(c) = c0;
+        // the accumulators start as NaN: the sweep itself must clear them, as the kernel must clear its LDS words
+        acc.assign((size_t)dsim_par_words((int)nd, (int)C), std::numeric_limits<float>::quiet_NaN());
+        c.pg = acc.data();
+        c.g_dof = g_dof ? g_dof + e * 5 * nd : nullptr;
+        c.g_contact = (g_contact && C) ? g_contact + e * 4 * C : nullptr;
+        sweep(c);
+    });
+}
+
 extern "C" int dsim_emu_env_forward(const dsim_model_desc* m, const dsim_env_spec* env, int n_envs, const float* q_in,
                                     const float* qd_in, const float* actions, float dt, int substeps, int mm_freq,
                                     float* q_out, float* qd_out, float* obs, float* rew, float* ckpt,
@@ -491,3 +522,6 @@ extern "C" long long dsim_emu_ckpt_floats(const dsim_model_desc* m, int substeps
 #include "dsim_emu_kin.cpp"
 #include "dsim_emu_dyn.cpp"
 #include "dsim_emu_jac.cpp"
+#include "dsim_emu_mass.cpp"
+#include "dsim_emu_con.cpp"
+#endif   // DSIM_EMU_EXECUTOR_ONLY

@@ -1,10 +1,8 @@
 // dsim_emu_con.cpp -- TEST-ONLY: the differentiable ground-contact read-out (dsim_core.hpp: dsim_ground_contact_forward /
 // dsim_ground_contact_backward) on the lane-serial host executor of dsim_emu.cpp, generic and specialised layouts, one or four
-// wavefronts per environment (dsim_emu_use_static / dsim_emu_set_waves of that file).  A translation unit of its own that
-// includes the harness; tests/con_lib.py builds it with the flags of tests/emu/Makefile.  Like dsim_emu.cpp it is not part of
-// the library.  Null pointers mean what they mean in include/dsim.h (dsim_ground_contacts, dsim_ground_contacts_backward).
-#include "dsim_emu.cpp"
-
+// wavefronts per environment (dsim_emu_use_static / dsim_emu_set_waves of that file).  Included at the end of dsim_emu.cpp
+// (one translation unit, tests/emu/Makefile); like that file it is not part of the library.  Null pointers mean what they mean in
+// include/dsim.h (dsim_ground_contacts, dsim_ground_contacts_backward).
 extern "C" int dsim_emu_ground_contacts(const dsim_model_desc* m, int n_envs, const float* q, const float* qd, float* point,
                                         float* vel, float* force, float* lw) {
     DsimLayout lay;

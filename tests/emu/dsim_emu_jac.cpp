@@ -1,34 +1,10 @@
 // dsim_emu_jac.cpp -- TEST-ONLY: the step Jacobian (dsim_core.hpp: dsim_multi_slot around dsim_sim_step_backward) on the
 // lane-serial host executor of dsim_emu.cpp, generic and specialised layouts, one or four wavefronts per environment, full or
 // lean checkpoints (dsim_emu_use_static / dsim_emu_set_waves / dsim_emu_set_ckpt_lean of that file).  Included at the end
-// of dsim_emu.cpp (one translation unit, tests/emu/Makefile); like that file it is not part of the library.  The multi entry points walk the block
+// of dsim_emu.cpp (one translation unit, tests/emu/Makefile); like that file it is not part of the library.  The entry points walk the block
 // indices of the device launch, 0 .. n_envs * n_cot - 1, and take every pointer from dsim_multi_slot -- the code the kernels
-// run; the single-sweep entry points do their own per-environment pointer arithmetic, as dsim_bwd_kernel does.
-extern "C" int dsim_emu_jac_forward(const dsim_model_desc* m, int n_envs, const float* q_in, const float* qd_in, const float* act,
-                                    const float* mact, float dt, int substeps, int mm_freq, float* q_out, float* qd_out, float* ckpt) {
-    DsimLayout lay;
-    if (!dsim_build_layout(*m, lay).empty()) return -1;
-    const size_t nq = lay.d.nq, nd = lay.d.nd, M = lay.d.M;
-    const size_t stride = dsim_ckpt_words(emu_row(lay), lay.d.nq, lay.d.nd, substeps, mm_freq);
-    return emu_each_env(lay, n_envs, dt / float(substeps), [&](auto& c, auto& ex, int e) {
-        dsim_sim_step_forward(c, ex, substeps, mm_freq, q_in + e * nq, qd_in + e * nd, act + e * nd, M ? mact + e * M : nullptr,
-                              q_out + e * nq, qd_out + e * nd, ckpt + e * stride);
-    });
-}
-
-extern "C" int dsim_emu_jac_backward(const dsim_model_desc* m, int n_envs, const float* ckpt, const float* act, const float* mact,
-                                     float dt, int substeps, int mm_freq, const float* gq_out, const float* gqd_out, float* gq_in,
-                                     float* gqd_in, float* gact, float* gmact) {
-    DsimLayout lay;
-    if (!dsim_build_layout(*m, lay).empty()) return -1;
-    const size_t nq = lay.d.nq, nd = lay.d.nd, M = lay.d.M;
-    const size_t stride = dsim_ckpt_words(emu_row(lay), lay.d.nq, lay.d.nd, substeps, mm_freq);
-    return emu_each_env(lay, n_envs, dt / float(substeps), [&](auto& c, auto& ex, int e) {
-        dsim_sim_step_backward(c, ex, substeps, mm_freq, ckpt + e * stride, act + e * nd, M ? mact + e * M : nullptr,
-                               gq_out + e * nq, gqd_out + e * nd, gq_in + e * nq, gqd_in + e * nd, gact ? gact + e * nd : nullptr,
-                               (gmact && M) ? gmact + e * M : nullptr);
-    });
-}
+// run; the single sweep with its own per-environment pointer arithmetic, as dsim_bwd_kernel does it, is dsim_emu_step_backward
+// of dsim_emu.cpp.
 
 // the device launch of dsim_bwd_multi_kernel, block by block
 static int jac_run_multi(const DsimLayout& lay, int n_envs, float dt, int substeps, int mm_freq, DsimMultiArgs a) {

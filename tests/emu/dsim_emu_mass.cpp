@@ -1,10 +1,8 @@
 // dsim_emu_mass.cpp -- TEST-ONLY: the differentiable mass matrix read-out (dsim_core.hpp: dsim_mass_forward / dsim_mass_backward)
 // on the lane-serial host executor of dsim_emu.cpp, generic and specialised layouts, one or four wavefronts per environment
-// (dsim_emu_use_static / dsim_emu_set_waves of that file).  A translation unit of its own that includes the harness;
-// tests/mass_lib.py builds it with the flags of tests/emu/Makefile.  Like dsim_emu.cpp it is not part of the library.  Null
-// pointers mean what they mean in include/dsim.h (dsim_mass_matrix, dsim_mass_matrix_backward).
-#include "dsim_emu.cpp"
-
+// (dsim_emu_use_static / dsim_emu_set_waves of that file).  Included at the end of dsim_emu.cpp (one translation unit,
+// tests/emu/Makefile); like that file it is not part of the library.  Null pointers mean what they mean in include/dsim.h
+// (dsim_mass_matrix, dsim_mass_matrix_backward).
 extern "C" int dsim_emu_mass_matrix(const dsim_model_desc* m, int n_envs, const float* q, float* H, float* Hinv, float* S) {
     DsimLayout lay;
     if (!dsim_build_layout(*m, lay).empty()) return -1;

@@ -1,7 +1,7 @@
 """Test infrastructure of the step Jacobian (dsim_step_backward_multi / dsim_step_jacobian):
 
 * the entry points of the lane-serial host harness for the block mapping (dsim_core.hpp: dsim_multi_slot) around the step
-  adjoint (tests/emu/dsim_emu_jac.cpp; tests/emu_lib.py loads the harness);
+  adjoint (tests/emu/dsim_emu_jac.cpp; tests/emu_lib.py loads the harness and has the single sweep, step_forward / step_backward);
 * the comparison against tests/golden/<env>_lin.npz (tools/gen_linearise_golden.py), shared by the host and the GPU tier.
 
 Bounds.  Every Jacobian block (J_qq, J_q_qd, J_qd_q, J_qd_qd, J_act, J_muscle) is compared in ITS OWN max-norm relative error,
@@ -20,8 +20,8 @@ import ctypes as C
 import numpy as np
 
 from diffrl_amd.capi import make_desc
-from emu_lib import f32, ptr, emu, mode
-from kin_lib import ENVS, waves_of  # noqa: F401
+from emu_lib import ENVS, waves_of  # noqa: F401
+from emu_lib import f32, ptr, emu, mode, step_backward, step_forward
 from oracle_lib import golden, project_tangent, template_from_golden
 
 BOUND, EXCLUDE, MAX_EXCLUDED = 1e-3, 1e-4, 1
@@ -32,17 +32,7 @@ _cases = {}
 
 def emu_forward(t, q, qd, act, mact, dt, S, mm, static=False, waves=1, lean=False):
     """-> (q_out, qd_out, ckpt)"""
-    desc, keep = make_desc(t)
-    q, qd, act = f32(q), f32(qd), f32(act)
-    N = q.shape[0]
-    mact = f32(mact) if t.n_muscles else None
-    with mode(emu(), static, waves, lean) as lib:
-        ck = np.zeros((N, int(lib.dsim_emu_ckpt_floats(C.byref(desc), C.c_int(S), C.c_int(mm)))), np.float32)
-        qo, qdo = np.zeros_like(q), np.zeros_like(qd)
-        rc = lib.dsim_emu_jac_forward(C.byref(desc), C.c_int(N), ptr(q), ptr(qd), ptr(act), ptr(mact), C.c_float(dt), C.c_int(S), C.c_int(mm),
-                                      ptr(qo), ptr(qdo), ptr(ck))
-    assert rc == 0, rc
-    return qo, qdo, ck
+    return step_forward(t, q, qd, act, mact, dt, S, mm, static=static, waves=waves, lean=lean)
 
 
 def _outputs(t, shape):
@@ -53,16 +43,8 @@ def _outputs(t, shape):
 
 def emu_backward(t, ck, act, mact, dt, S, mm, gq_out, gqd_out, static=False, waves=1, lean=False):
     """one sweep per environment, the pointer arithmetic of dsim_bwd_kernel -> (gq_in, gqd_in, gact, gmact | None)"""
-    desc, keep = make_desc(t)
-    ck, act, gq_out, gqd_out = f32(ck), f32(act), f32(gq_out), f32(gqd_out)
-    mact = f32(mact) if t.n_muscles else None
-    N = ck.shape[0]
-    out = _outputs(t, (N,))
-    with mode(emu(), static, waves, lean) as lib:
-        rc = lib.dsim_emu_jac_backward(C.byref(desc), C.c_int(N), ptr(ck), ptr(act), ptr(mact), C.c_float(dt), C.c_int(S), C.c_int(mm),
-                                       ptr(gq_out), ptr(gqd_out), *[ptr(o) for o in out])
-    assert rc == 0, rc
-    return out
+    r = step_backward(t, ck, act, mact, dt, S, mm, gq_out, gqd_out, static=static, waves=waves, lean=lean)
+    return r["gq"], r["gqd"], r["gact"], r["gmact"]
 
 
 def emu_backward_multi(t, ck, act, mact, dt, S, mm, gq_out, gqd_out, shared, static=False, waves=1, lean=False):

@@ -6,23 +6,12 @@
   section 3), the reference for models the reference simulator has no recording of.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from diffrl_amd.capi import make_desc
+from emu_lib import ENVS, USER_MODELS, waves_of  # noqa: F401
 from emu_lib import f32, ptr, emu, emu_user, mode
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENVS = ("ant", "humanoid", "snu", "hopper", "cartpole", "cheetah")
-USER_MODELS = (("UserTree", os.path.join(ROOT, "tests", "golden", "user_tree.npz")),
-               ("UserRowTree", os.path.join(ROOT, "tests", "golden", "user_rowtree.npz")))
-
-def waves_of(t):
-    """wavefronts per environment the library picks for this model (dsim_hip.hip: pick_waves)"""
-    from diffrl_amd import specialise
-    d = specialise.layout(t)[1]
-    return 4 if (d["NS"] > 64 or d["C"] > 64) else 1
 
 
 def emu_kin_forward(t, q, qd, static=False, waves=1, user=False, want_xsm=True):

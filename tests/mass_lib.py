@@ -1,67 +1,31 @@
 """Test infrastructure of the differentiable mass matrix read-out (dsim_mass_matrix / dsim_mass_matrix_backward):
 
-* the host harness for this phase code, tests/emu/dsim_emu_mass.cpp (a translation unit that includes dsim_emu.cpp), compiled here
-  with the flags of tests/emu/Makefile to tests/emu/libdsim_emu_mass.so (and libdsim_emu_mass_user.so with the layouts of the two
-  user models) when it is older than its sources, and its entry points;
+* the entry points of the lane-serial host harness for this phase code (tests/emu/dsim_emu_mass.cpp; tests/emu_lib.py loads the
+  harness), for the shipped layouts and for the two user models of tests/golden/user_*.npz;
 * a float32 numpy restatement of the pivot-free Gauss-Jordan elimination (classical form, written from the formulas alone): the
   yardstick of the residual |Hinv H - I| that an fp32 inverse of THIS matrix can be expected to reach;
 * the bounds and the link / dof incidence mask the two test tiers share.
 """
 import ctypes as C
-import os
-import re
-import shlex
-import subprocess
 
 import numpy as np
 
 from diffrl_amd.capi import make_desc
-from emu_lib import EMU_DIR, f32, mode, ptr
+from emu_lib import ENVS, ROOT  # noqa: F401
+from emu_lib import emu, emu_user, f32, mode, ptr
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENVS = ("ant", "humanoid", "snu", "hopper", "cartpole", "cheetah")
 SETS = ("H", "Hinv", "S", "all")
 FWD_BOUND = 1e-5      # S and H in the tensor's max-norm: the bound of the first-substep S_s and I_s (tests/ckpt_fields.py)
 SYM_BOUND = 1e-6      # max |H - H^T| / max |H|
 RADIAL = 1e-6
 RESIDUAL_FACTOR, RESIDUAL_FLOOR = 10.0, 1e-6
 FD_STEP, FD_BOUND = 1e-2, 1e-3
-_libs = {}
-
-
-def _make_var(name):
-    src = open(os.path.join(EMU_DIR, "Makefile")).read().replace("\\\n", " ")
-    return re.search(r"^%s\s*\??=\s*(.*)$" % name, src, re.M).group(1).strip()
-
-
-def _harness(user):
-    """libdsim_emu_mass.so / libdsim_emu_mass_user.so: rebuilt when older than a source of the harness, loaded once"""
-    name = "libdsim_emu_mass_user.so" if user else "libdsim_emu_mass.so"
-    if name not in _libs:
-        so = os.path.join(EMU_DIR, name)
-        deps = [os.path.normpath(os.path.join(EMU_DIR, s)) for s in _make_var("SRC").split()] + [os.path.join(EMU_DIR, "dsim_emu_mass.cpp")]
-        flags = []
-        if user:
-            hdr = os.path.join(ROOT, "tests", "inject", "dsim_static_layouts_user.hpp")
-            if not os.path.exists(hdr):
-                raise RuntimeError("tests/inject/dsim_static_layouts_user.hpp is missing: __graft_entry__.build() generates it")
-            deps.append(hdr)
-            flags = ['-DDSIM_STATIC_LAYOUTS_FILE="../inject/dsim_static_layouts_user.hpp"',
-                     "-DDSIM_STATIC_VARIANTS(X)=X(UserTree) X(UserRowTree)"]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            cxx = os.environ.get("CXX") or _make_var("CXX")
-            tmp = so + ".%d.tmp" % os.getpid()
-            subprocess.check_call([cxx] + shlex.split(_make_var("CXXFLAGS")) + flags + ["-shared", "-o", tmp, "dsim_emu_mass.cpp"],
-                                  cwd=EMU_DIR)
-            os.replace(tmp, so)
-        _libs[name] = C.CDLL(so)
-    return _libs[name]
 
 
 def emu_mass_forward(t, q, static=False, waves=1, user=False, want=(True, True, True)):
     """-> (H [N, nd, nd], Hinv [N, nd, nd], S [N, nd, 6]); an output not wanted is passed as NULL and returned as None.  The
     buffers start as NaN: what comes back was written."""
-    lib = _harness(user)
+    lib = emu_user() if user else emu()
     desc, keep = make_desc(t)
     q = f32(q)
     N, nd = q.shape[0], t.n_qd
@@ -74,7 +38,7 @@ def emu_mass_forward(t, q, static=False, waves=1, user=False, want=(True, True, 
 
 
 def emu_mass_backward(t, q, gH, gHinv, gS, static=False, waves=1, user=False):
-    lib = _harness(user)
+    lib = emu_user() if user else emu()
     desc, keep = make_desc(t)
     q, gH, gHinv, gS = f32(q), f32(gH), f32(gHinv), f32(gS)
     gq = np.full((q.shape[0], t.n_q), np.nan, np.float32)

@@ -1,102 +1,36 @@
 """Test infrastructure of the model-parameter gradients of the step (dsim_model_set_params / dsim_step_backward_params):
 
-* the host harness for this phase code, tests/emu/dsim_emu_par.cpp (a translation unit that includes dsim_emu.cpp), compiled here
-  with the flags of tests/emu/Makefile to tests/emu/libdsim_emu_par.so when it is older than its sources, and its entry points;
+* the step of the lane-serial host harness with a parameter block and with the parameter gradients (dsim_emu_step_forward /
+  dsim_emu_step_backward of tests/emu/dsim_emu.cpp through emu_lib.step_forward / step_backward; tests/emu_lib.py loads the harness);
 * the folds from what the kernels return -- per dof [N][5][nd], per contact slot [N][C][4] -- to what the reference records per
   environment: per link, per coordinate (target) and per SHAPE (contact_material of <env>_model.npz is the shape of each slot);
 * the bounds the two test tiers share.
 """
-import ctypes as C
-import os
-import re
-import shlex
-import subprocess
-
 import numpy as np
 
-from diffrl_amd.capi import make_desc
-from emu_lib import EMU_DIR, f32, mode, ptr
+from emu_lib import ENVS, ROOT  # noqa: F401
+from emu_lib import PARAM_FIELDS as FIELDS
+from emu_lib import step_backward, step_forward
 from oracle_lib import golden, template_from_golden
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENVS = ("ant", "humanoid", "snu", "hopper", "cartpole", "cheetah")
-FIELDS = ("target_ke", "target_kd", "limit_ke", "limit_kd", "target", "contact_material")   # order of DSIM_PARAM_*
 DOF_ROWS = ("target_ke", "target_kd", "target", "limit_ke", "limit_kd")                     # rows of g_dof
 PARAM_TENSORS = ("g_target_ke", "g_target_kd", "g_target", "g_limit_ke", "g_limit_kd", "g_shape_materials")
 # forward outputs and state gradients: the bounds of the step tests (tests/test_emu_phases.py, tests/test_gpu_parity.py)
 STATE_BOUND, GRAD_BOUND = 1e-4, 1e-3
 HINGE = (0, 1)
-_lib = None
-
-
-def _make_var(name):
-    src = open(os.path.join(EMU_DIR, "Makefile")).read().replace("\\\n", " ")
-    return re.search(r"^%s\s*\??=\s*(.*)$" % name, src, re.M).group(1).strip()
-
-
-def _harness():
-    """libdsim_emu_par.so: rebuilt when older than a source of the harness, loaded once"""
-    global _lib
-    if _lib is None:
-        so = os.path.join(EMU_DIR, "libdsim_emu_par.so")
-        deps = [os.path.normpath(os.path.join(EMU_DIR, s)) for s in _make_var("SRC").split()] + [os.path.join(EMU_DIR, "dsim_emu_par.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-            cxx = os.environ.get("CXX") or _make_var("CXX")
-            tmp = so + ".%d.tmp" % os.getpid()
-            subprocess.check_call([cxx] + shlex.split(_make_var("CXXFLAGS")) + ["-shared", "-o", tmp, "dsim_emu_par.cpp"], cwd=EMU_DIR)
-            os.replace(tmp, so)
-        _lib = C.CDLL(so)
-        _lib.dsim_emu_ckpt_floats.restype = C.c_longlong
-    return _lib
-
-
-def _params(p):
-    """dict field -> array (missing: the template's) -> (array of six pointers or None, keepalive)"""
-    if not p:
-        return None, None
-    arrs = [f32(p[k]) if p.get(k) is not None else None for k in FIELDS]
-    return (C.c_void_p * 6)(*[ptr(a) for a in arrs]), arrs
 
 
 def emu_par_forward(t, q, qd, act, mact, dt, substeps, mm_freq, params=None, static=False, waves=1, lean=False):
     """-> (q_out, qd_out, ckpt); buffers start as NaN"""
-    lib = _harness()
-    desc, keep = make_desc(t)
-    q, qd, act = f32(q), f32(qd), f32(act)
-    N = q.shape[0]
-    mact = f32(mact) if mact is not None else np.zeros((N, 0), np.float32)
-    pp, keep2 = _params(params)
-    qo, qdo = np.full_like(q, np.nan), np.full_like(qd, np.nan)
-    with mode(lib, static, waves, lean):
-        ck = np.zeros((N, int(lib.dsim_emu_ckpt_floats(C.byref(desc), C.c_int(substeps), C.c_int(mm_freq)))), np.float32)
-        rc = lib.dsim_emu_par_forward(C.byref(desc), pp, C.c_int(N), ptr(q), ptr(qd), ptr(act), ptr(mact), C.c_float(dt),
-                                      C.c_int(substeps), C.c_int(mm_freq), ptr(qo), ptr(qdo), ptr(ck))
-    assert rc == 0, rc
-    return qo, qdo, ck
+    return step_forward(t, q, qd, act, mact, dt, substeps, mm_freq, params=params, static=static, waves=waves, lean=lean)
 
 
 def emu_par_backward(t, ckpt, act, mact, dt, substeps, mm_freq, gq_out, gqd_out, params=None, static=False, waves=1, lean=False,
                      want=(True, True), want_act=True):
     """want = (g_dof, g_contact); both False: the plain step adjoint.  -> dict(gq, gqd, gact, gmact, g_dof, g_contact); an output
     not wanted is passed as NULL and returned as None; the buffers start as NaN: what comes back was written."""
-    lib = _harness()
-    desc, keep = make_desc(t)
-    ckpt, act, gq_out, gqd_out = f32(ckpt), f32(act), f32(gq_out), f32(gqd_out)
-    N, nd, Cn, M = act.shape[0], t.n_qd, t.n_contacts, t.n_muscles
-    mact = f32(mact) if mact is not None else np.zeros((N, 0), np.float32)
-    pp, keep2 = _params(params)
-    nan = lambda *s: np.full(s, np.nan, np.float32)  # noqa: E731
-    gq, gqd = nan(N, t.n_q), nan(N, nd)
-    ga = nan(N, nd) if want_act else None
-    gm = nan(N, M) if (want_act and M) else None
-    g_dof = nan(N, 5, nd) if want[0] else None
-    g_con = nan(N, Cn, 4) if want[1] else None
-    with mode(lib, static, waves, lean):
-        rc = lib.dsim_emu_par_backward(C.byref(desc), pp, C.c_int(N), ptr(ckpt), ptr(act), ptr(mact), C.c_float(dt), C.c_int(substeps),
-                                       C.c_int(mm_freq), ptr(gq_out), ptr(gqd_out), ptr(gq), ptr(gqd), ptr(ga), ptr(gm), ptr(g_dof),
-                                       ptr(g_con))
-    assert rc == 0, rc
-    return dict(gq=gq, gqd=gqd, gact=ga, gmact=gm, g_dof=g_dof, g_contact=g_con)
+    return step_backward(t, ckpt, act, mact, dt, substeps, mm_freq, gq_out, gqd_out, params=params, static=static, waves=waves,
+                         lean=lean, want=want, want_act=want_act)
 
 
 # ---- folds -------------------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <random>
 
+#define DSIM_EMU_EXECUTOR_ONLY   // (HostExec alone: no entry points of the harness)
 #include "../emu/dsim_emu.cpp"
 
 namespace {

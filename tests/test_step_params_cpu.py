@@ -1,6 +1,6 @@
 """CPU: the step adjoint with model-parameter gradients (dsim_core.hpp: DsimParCtxT around dsim_sim_step_backward, the code of
-dsim_bwd_param_kernel) on the lane-serial host build of the phase code (tests/emu/dsim_emu_par.cpp, compiled by tests/par_lib.py):
-all six models, generic and specialised layouts, one and four wavefronts per environment, full and lean checkpoints.
+dsim_bwd_param_kernel) on the lane-serial host build of the phase code (dsim_emu_step_backward of tests/emu/dsim_emu.cpp through
+tests/par_lib.py): all six models, generic and specialised layouts, one and four wavefronts per environment, full and lean checkpoints.
 
 Reference: tests/golden/<env>_par.npz, the reference simulator's own tape replay of three substeps (mass matrix refreshed on
 substeps 0 and 2) with requires_grad on its model tensors (tools/gen_param_golden.py); the library runs the same step as
