@@ -3374,6 +3374,17 @@ template <class Ctx, class Exec> DSIM_FN void dsim_hacc_zero(const Ctx& c, Exec&
         }
     }
 }
+// Entering a mass-matrix group in the reverse sweep, per lane: hinv <- the inverse the group's forward substeps used (hv, global
+// memory), aH <- 0, and the lane's accumulator registers.  STRIDE lanes share the words, `lane` is this one's index among them;
+// acc_lane: the lane whose accumulator it clears (its own index in the workgroup where the STRIDE lanes are not the first ones).
+template <int STRIDE, class Ctx, class Exec> DSIM_FN void dsim_group_enter(const Ctx& c, Exec& ex, int lane, const float* hv, int acc_lane) {
+    const int nn = c.d.nd * c.d.nd;
+    for (int k = lane; k < nn; k += STRIDE) {
+        WF(hinv)[k] = hv[k];
+        WF(aH)[k] = 0.f;
+    }
+    dsim_hacc_zero(c, ex, acc_lane);
+}
 
 // Joint-space adjoint of the models whose links other than the free root have one hinge / prismatic dof each (DsimDims::JW_OK,
 // JW_FREE_ROOT: Ant; Humanoid, Hopper and HalfCheetah qualify structurally and measured no gain), up to DSIM_JW_ND_MAX dofs: integrate^T, adj tau = H^-1 adj qdd and the per-dof cotangents of
@@ -4698,13 +4709,7 @@ template <class Ctx, class Exec> DSIM_FN void dsim_bwd_bodies_rowtree(const Ctx&
             }
             if (nx.any) {
                 ex.commit_rest(WF(q), dsim_row(c), lane);
-                if (nx.hv) {
-                    for (int k = lane; k < c.d.nd * c.d.nd; k += NLR) {
-                        WF(hinv)[k] = nx.hv[k];
-                        WF(aH)[k] = 0.f;
-                    }
-                    dsim_hacc_zero(c, ex, lane + DSIM_NL);
-                }
+                if (nx.hv) dsim_group_enter<NLR>(c, ex, lane, nx.hv, lane + DSIM_NL);
                 if (nx.after) ex.prefetch_rest(nx.after, dsim_row(c));
             }
         });
@@ -4791,14 +4796,112 @@ template <class Ctx, class Exec> struct DsimWideRows {
     }();
 };
 
+// What a driver of dsim_bwd_sweep has done in front of it.  Compile-time: flags inside the substep loops cost the kernels SGPR
+// spills (see dsim_joint_regs_begin).
+//   ROW_REQUESTED  the last substep's checkpoint row, the first the sweep commits, is requested (Exec::prefetch; helper kernels:
+//                  Exec::helper_prefetch, and Exec::group_sync has been issued behind the driver's last use of q / qd, the words
+//                  the row lands on).  false: the sweep requests it on the spot.
+//   HPF            > 0: the last group's inverse waits in that many registers per lane (Exec::hpf, entry lane + NL * r in r)
+//   HINV_IN_LDS    the helper wavefront brings the last group's inverse and zeroes aH (Exec::helper_commit_aux), and the
+//                  accumulator registers are cleared: the sweep must not load that group's inverse again
+// Neither of the last two: the sweep loads the last group's inverse on the spot, as it loads every other group's.
+template <bool ROW_REQUESTED, int HPF, bool HINV_IN_LDS> struct DsimSweepEntry {
+    static constexpr bool row_requested = ROW_REQUESTED, hinv_in_lds = HINV_IN_LDS;
+    static constexpr int hpf = HPF;
+};
+// The reverse sweep over the substeps of one launch: THE reverse statement of the refresh schedule (the forward drivers write
+// theirs out: substep s refreshes iff s % mm_freq == 0) and of the checkpoint pipeline of every executor.  Groups of mm_freq substeps, the last one possibly shorter, from
+// the last to the first; entering a group, the inverse its forward substeps used replaces hinv and the accumulated cotangent of
+// the mass matrix restarts from zero (dsim_group_enter); the group's first substep s0, reached last, is its refresh substep: the
+// composite-body pass in front of it, the mass-matrix adjoint inside it.
+// In: aqn / aqdn = the cotangents of the launch's end state, aact / amact = 0, act / mact, the topology records.  Out: aqn / aqdn
+// (== aq / aqd, same LDS words) = the cotangents of its start state, aact / amact summed over the substeps.
+// g_lit (dsim_step_backward_literal; null for every other caller, folded away): this environment's [nq + nd + nd * nd] words --
+// the cotangents of the FIRST substep's outputs (q_1, qd_1) and the mass-matrix cotangent of the first group, what
+// dsim_literal.hpp contracts its tangent with.
+template <class Entry, class Ctx, class Exec>
+DSIM_FN void dsim_bwd_sweep(const Ctx& c, Exec& ex, int substeps, int mm_freq, const float* g_ckpt, float* g_lit = nullptr) {
+    const int nq = c.d.nq, nd = c.d.nd;
+    constexpr bool HELPER = DsimHelperCommit<Ctx, Exec>::value, WIDE = DsimWideRows<Ctx, Exec>::value;
+    static_assert(HELPER || !Entry::hinv_in_lds, "only the helper wavefront brings an inverse to LDS ahead of the sweep");
+    static_assert(!HELPER || Entry::hpf == 0, "helper kernels get the last group's inverse through the helper or on the spot");
+    auto row = [&](int s) __attribute__((always_inline)) { return g_ckpt + (size_t)s * dsim_row(c); };
+    // entering a group on the lanes of a commit phase; last: it is the last group, whose inverse the driver may hold in registers
+    auto enter = [&](int lane, const float* hv, bool last) __attribute__((always_inline)) {
+        if (Entry::hpf > 0 && last) {
+            const float* hpf = ex.hpf(lane);
+#pragma unroll
+            for (int r = 0; r < Entry::hpf; ++r) {
+                const int k = lane + Exec::NL * r;
+                if (k < nd * nd) {
+                    WF(hinv)[k] = hpf[r];
+                    WF(aH)[k] = 0.f;
+                }
+            }
+            dsim_hacc_zero(c, ex, lane);
+        } else {
+            dsim_group_enter<Exec::NL>(c, ex, lane, hv, lane);
+        }
+    };
+    const int groups = (substeps + mm_freq - 1) / mm_freq;
+    for (int g = groups - 1; g >= 0; --g) {
+        const int s0 = g * mm_freq, s1 = (s0 + mm_freq < substeps) ? s0 + mm_freq : substeps;
+        for (int s = s1 - 1; s >= s0; --s) {
+            // forward intermediates of substep s (and, entering a group, the inverse its substeps used) from HBM.
+            // The row was requested one substep earlier (ex.prefetch keeps it in flight in registers while the
+            // previous adjoint substep computes), so this phase only moves registers to LDS.
+            const float* hv = (s == s1 - 1 && !(Entry::hinv_in_lds && g == groups - 1)) ? dsim_ckpt_hinv(c, const_cast<float*>(g_ckpt), substeps, g) : nullptr;
+            if constexpr (HELPER) {
+                if (!Entry::row_requested && s == substeps - 1) {
+                    ex.helper_prefetch(row(s), dsim_row(c));
+                    ex.group_sync();   // the main wave is done with the prologue's use of q / qd (the words the row lands on)
+                }
+                ex.helper_commit(WF(q), dsim_row(c), s > 0 ? row(s - 1) : nullptr);
+                if (hv) ex.run([&](int lane) { enter(lane, hv, false); });   // (helper kernels: Entry::hpf == 0)
+            } else if constexpr (WIDE) {
+                // only the launch's first row is committed here, every later one -- with its group's inverse -- by the body level of
+                // the substep before it
+                if (s == substeps - 1) {
+                    if (!Entry::row_requested) ex.prefetch(row(s), dsim_row(c));
+                    ex.run([&](int lane) {
+                        ex.commit(WF(q), dsim_row(c), lane);
+                        enter(lane, hv, true);
+                    });
+                    if (s > 0) ex.prefetch_rest(row(s - 1), dsim_row(c));
+                }
+            } else {
+                if (!Entry::row_requested && s == substeps - 1) ex.prefetch(row(s), dsim_row(c));
+                ex.run([&](int lane) {
+                    ex.commit(WF(q), dsim_row(c), lane);
+                    if (hv) enter(lane, hv, g == groups - 1);
+                });
+                if (s > 0) ex.prefetch(row(s - 1), dsim_row(c));
+            }
+            if constexpr (Ctx::LEAN) dsim_bwd_recompute_forward(c, ex);
+            if (s == s0) dsim_fwd_composite(c, ex);
+            DsimNextRow nx;
+            if constexpr (WIDE) {
+                nx.any = s > 0;
+                nx.hv = (s == s0 && g > 0) ? dsim_ckpt_hinv(c, const_cast<float*>(g_ckpt), substeps, g - 1) : nullptr;
+                nx.after = s > 1 ? row(s - 2) : nullptr;
+            }
+            if (g_lit && s == 0)
+                ex.fire([&](int lane) {
+                    for (int k = lane; k < nq; k += Exec::NL) g_lit[k] = WF(aqn)[k];
+                    for (int k = lane; k < nd; k += Exec::NL) g_lit[nq + k] = WF(aqdn)[k];
+                });
+            dsim_bwd_substep(c, ex, s == s0, nx, (g_lit && s == 0) ? g_lit + nq + nd : nullptr);  // aq / aqd (== aqn / aqdn, same LDS words) now belong to substep s - 1
+        }
+    }
+}
+
 // Reverse sweep of one env.step().  g_ckpt is this environment's [substeps][nq+nd] checkpoint.
 template <class Ctx, class Exec>
 DSIM_FN void dsim_sim_step_backward(const Ctx& c, Exec& ex, int substeps, int mm_freq, const float* g_ckpt,
                                     const float* g_act, const float* g_mact, const float* g_gq_out,
                                     const float* g_gqd_out, float* g_gq_in, float* g_gqd_in, float* g_gact,
                                     float* g_gmact, float* g_lit = nullptr) {
-    // g_lit (dsim_step_backward_literal): this environment's [nq + nd + nd * nd] words -- the cotangents of the FIRST substep's
-    // outputs (q_1, qd_1) and the mass-matrix cotangent of the first group, what dsim_literal.hpp contracts its tangent with
+    // g_lit (dsim_step_backward_literal only): see dsim_bwd_sweep
     const int nq = c.d.nq, nd = c.d.nd, M = c.d.M;
     ex.begin_request();
     ex.begin();
@@ -4818,72 +4921,7 @@ DSIM_FN void dsim_sim_step_backward(const Ctx& c, Exec& ex, int substeps, int mm
         if constexpr (DsimParamGrad<Ctx>::value)
             for (int k = lane; k < dsim_par_words(nd, c.d.C); k += Exec::NL) c.pg[k] = 0.f;
     });
-    const int groups = (substeps + mm_freq - 1) / mm_freq;
-    for (int g = groups - 1; g >= 0; --g) {
-        const int s0 = g * mm_freq, s1 = (s0 + mm_freq < substeps) ? s0 + mm_freq : substeps;
-        for (int s = s1 - 1; s >= s0; --s) {
-            // forward intermediates of substep s (and, entering a group, the inverse its substeps used) from HBM.
-            // The row was requested one substep earlier (ex.prefetch keeps it in flight in registers while the
-            // previous adjoint substep computes), so this phase only moves registers to LDS.
-            const float* hv = (s == s1 - 1) ? dsim_ckpt_hinv(c, const_cast<float*>(g_ckpt), substeps, g) : nullptr;
-            if constexpr (DsimHelperCommit<Ctx, Exec>::value) {
-                if (s == substeps - 1) {
-                    ex.helper_prefetch(g_ckpt + (size_t)s * dsim_row(c), dsim_row(c));
-                    ex.group_sync();   // the main wave is done with the prologue's use of q / qd (the words the row lands on)
-                }
-                ex.helper_commit(WF(q), dsim_row(c), s > 0 ? g_ckpt + (size_t)(s - 1) * dsim_row(c) : nullptr);
-                if (hv)
-                    ex.run([&](int lane) {
-                        for (int k = lane; k < nd * nd; k += Exec::NL) {
-                            WF(hinv)[k] = hv[k];
-                            WF(aH)[k] = 0.f;
-                        }
-                        dsim_hacc_zero(c, ex, lane);
-                    });
-            } else if constexpr (DsimWideRows<Ctx, Exec>::value) {
-                // only the launch's first row is committed here; every later one by the body level of the substep before it
-                if (s == substeps - 1) {
-                    ex.prefetch(g_ckpt + (size_t)s * dsim_row(c), dsim_row(c));
-                    ex.run([&](int lane) {
-                        ex.commit(WF(q), dsim_row(c), lane);
-                        for (int k = lane; k < nd * nd; k += Exec::NL) {
-                            WF(hinv)[k] = hv[k];
-                            WF(aH)[k] = 0.f;
-                        }
-                        dsim_hacc_zero(c, ex, lane);
-                    });
-                    if (s > 0) ex.prefetch_rest(g_ckpt + (size_t)(s - 1) * dsim_row(c), dsim_row(c));
-                }
-            } else {
-                if (s == substeps - 1) ex.prefetch(g_ckpt + (size_t)s * dsim_row(c), dsim_row(c));
-                ex.run([&](int lane) {
-                    ex.commit(WF(q), dsim_row(c), lane);
-                    if (hv) {
-                        for (int k = lane; k < nd * nd; k += Exec::NL) {
-                            WF(hinv)[k] = hv[k];
-                            WF(aH)[k] = 0.f;
-                        }
-                        dsim_hacc_zero(c, ex, lane);
-                    }
-                });
-                if (s > 0) ex.prefetch(g_ckpt + (size_t)(s - 1) * dsim_row(c), dsim_row(c));
-            }
-            if constexpr (Ctx::LEAN) dsim_bwd_recompute_forward(c, ex);
-            if (s == s0) dsim_fwd_composite(c, ex);
-            DsimNextRow nx;
-            if constexpr (DsimWideRows<Ctx, Exec>::value) {
-                nx.any = s > 0;
-                nx.hv = (s == s0 && g > 0) ? dsim_ckpt_hinv(c, const_cast<float*>(g_ckpt), substeps, g - 1) : nullptr;
-                nx.after = s > 1 ? g_ckpt + (size_t)(s - 2) * dsim_row(c) : nullptr;
-            }
-            if (g_lit && s == 0)
-                ex.fire([&](int lane) {
-                    for (int k = lane; k < nq; k += Exec::NL) g_lit[k] = WF(aqn)[k];
-                    for (int k = lane; k < nd; k += Exec::NL) g_lit[nq + k] = WF(aqdn)[k];
-                });
-            dsim_bwd_substep(c, ex, s == s0, nx, (g_lit && s == 0) ? g_lit + nq + nd : nullptr);  // aq / aqd (== aqn / aqdn, same LDS words) now belong to substep s - 1
-        }
-    }
+    dsim_bwd_sweep<DsimSweepEntry<false, 0, false>>(c, ex, substeps, mm_freq, g_ckpt, g_lit);
     ex.run([&](int lane) {
         for (int k = lane; k < nq; k += Exec::NL) g_gq_in[k] = WF(aqn)[k];
         for (int k = lane; k < nd; k += Exec::NL) {
@@ -5503,7 +5541,7 @@ DSIM_FN void dsim_env_fused_backward(const Ctx& c, Exec& ex, const DsimEnvSpec& 
     // The inverse of the LAST group of substeps (the first the adjoint needs) is requested here and stored to LDS at the first
     // substep: its memory latency (measured: 2.4 k cycles of the Ant adjoint launch when loaded on the spot) passes under the
     // observation adjoint, whose serial quaternion chain on one lane needs no memory at all.
-    const int groups = (substeps + mm_freq - 1) / mm_freq;
+    const int groups = (substeps + mm_freq - 1) / mm_freq;   // (as in dsim_bwd_sweep: groups - 1 is the group it enters first)
     // (helper-wave kernels: the helper brings it, if its registers hold it -- 4 x 64 x Exec::DSIM_APF words; a bigger model's main
     // wave loads it on the spot, as before)
     constexpr bool helper_aux = []() {
@@ -5534,13 +5572,6 @@ DSIM_FN void dsim_env_fused_backward(const Ctx& c, Exec& ex, const DsimEnvSpec& 
             for (int r = 0; r < HPF; ++r) hpf[r] = hv[(lane + Exec::NL * r) < nd * nd ? lane + Exec::NL * r : 0];
         });
     }
-    // hinv <- a group's inverse, aH <- 0
-    auto load_hinv = [&](int lane, const float* hv) __attribute__((always_inline)) {
-        for (int k = lane; k < nd * nd; k += Exec::NL) {
-            WF(hinv)[k] = hv[k];
-            WF(aH)[k] = 0.f;
-        }
-    };
     dsim_init_static(c, ex);
     ex.run_both([&](int lane) { dsim_topo_init(c, ex, lane); });   // every wave keeps its own topology records
     // (helper wavefront) the inverse of the last group of substeps, the first the adjoint needs: requested now -- behind the
@@ -5573,69 +5604,18 @@ DSIM_FN void dsim_env_fused_backward(const Ctx& c, Exec& ex, const DsimEnvSpec& 
     });
     dsim_env_load_actions(c, ex, sp, g_actions, true);
     dsim_env_observe_adjoint(c, ex, sp, g_gobs, g_grew, g_gobs_before, ep_flags, true);
-    // The first inverse goes to LDS HERE, in front of the loops: a use inside them would keep the registers it waits in alive
-    // through every substep (measured: Humanoid's helper kernel 255 -> 271 VGPRs).
+    // The helper's inverse goes to LDS HERE, in front of the sweep: a use inside its loops would keep the registers it waits in
+    // alive through every substep (measured: Humanoid's helper kernel 255 -> 271 VGPRs).
     // (Kernels without a helper keep theirs in the loop: a phase of its own costs the four-wave SNUHumanoid kernel 2 %.)
-    constexpr bool first_hinv_ahead = helper_aux;
-    if constexpr (DsimHelperCommit<Ctx, Exec>::value) ex.group_sync();   // the main wave is done with the end state in q / qd (observation adjoint)
+    if constexpr (DsimHelperCommit<Ctx, Exec>::value) {
+        static_assert(IO::PRE, "helper-side commit belongs to the specialised kernels: the row is requested above");
+        ex.group_sync();   // the main wave is done with the end state in q / qd (observation adjoint)
+    }
     if constexpr (helper_aux) {
         ex.helper_commit_aux(WF(hinv), WF(aH), dsim_hinv_words_d(nd));   // (published by the barrier of the first helper_commit)
         ex.fire([&](int lane) { dsim_hacc_zero(c, ex, lane); });
     }
-    for (int g = groups - 1; g >= 0; --g) {
-        const int s0 = g * mm_freq, s1 = (s0 + mm_freq < substeps) ? s0 + mm_freq : substeps;
-        for (int s = s1 - 1; s >= s0; --s) {
-            // forward intermediates of substep s (and, entering a group, the inverse its substeps used) from HBM.
-            // The row was requested one substep earlier (ex.prefetch keeps it in flight in registers while the
-            // previous adjoint substep computes), so this phase only moves registers to LDS.
-            const float* hv = (s == s1 - 1 && !(first_hinv_ahead && g == groups - 1)) ? dsim_ckpt_hinv(c, const_cast<float*>(g_ckpt), substeps, g) : nullptr;
-            if constexpr (DsimHelperCommit<Ctx, Exec>::value) {
-                static_assert(IO::PRE, "helper-side commit belongs to the specialised kernels");
-                ex.helper_commit(WF(q), dsim_row(c), s > 0 ? g_ckpt + (size_t)(s - 1) * dsim_row(c) : nullptr);
-                if (hv)
-                    ex.run([&](int lane) {
-                        load_hinv(lane, hv);
-                        dsim_hacc_zero(c, ex, lane);
-                    });
-            } else if (!DsimWideRows<Ctx, Exec>::value || s == substeps - 1) {
-                // (DsimWideRows: only the launch's first row is committed here, every later one -- with its group's inverse -- by the
-                // body level of the substep before it)
-                if (!IO::PRE && s == substeps - 1) ex.prefetch(g_ckpt + (size_t)s * dsim_row(c), dsim_row(c));
-                ex.run([&](int lane) {
-                    ex.commit(WF(q), dsim_row(c), lane);
-                    if (hv) {
-                        if (HPF > 0 && g == groups - 1) {
-                            const float* hpf = ex.hpf(lane);
-#pragma unroll
-                            for (int r = 0; r < HPF; ++r) {
-                                const int k = lane + Exec::NL * r;
-                                if (k < nd * nd) {
-                                    WF(hinv)[k] = hpf[r];
-                                    WF(aH)[k] = 0.f;
-                                }
-                            }
-                        } else {
-                            load_hinv(lane, hv);
-                        }
-                        dsim_hacc_zero(c, ex, lane);
-                    }
-                });
-                if (s > 0) {
-                    if constexpr (DsimWideRows<Ctx, Exec>::value) ex.prefetch_rest(g_ckpt + (size_t)(s - 1) * dsim_row(c), dsim_row(c));
-                    else ex.prefetch(g_ckpt + (size_t)(s - 1) * dsim_row(c), dsim_row(c));
-                }
-            }
-            if constexpr (Ctx::LEAN) dsim_bwd_recompute_forward(c, ex);
-            if (s == s0) dsim_fwd_composite(c, ex);
-            DsimNextRow nx;
-            if constexpr (DsimWideRows<Ctx, Exec>::value) {
-                nx.any = s > 0;
-                nx.hv = (s == s0 && g > 0) ? dsim_ckpt_hinv(c, const_cast<float*>(g_ckpt), substeps, g - 1) : nullptr;
-                nx.after = s > 1 ? g_ckpt + (size_t)(s - 2) * dsim_row(c) : nullptr;
-            }
-            dsim_bwd_substep(c, ex, s == s0, nx);  // aq / aqd (== aqn / aqdn, same LDS words) now belong to substep s - 1
-        }
-    }
+    dsim_bwd_sweep<DsimSweepEntry<IO::PRE, HPF, helper_aux>>(c, ex, substeps, mm_freq, g_ckpt);
     // sanitize: torch.nan_to_num(grad, 0.0, 0.0, 0.0) of the reference's per-step hooks on joint_q / joint_qd / actions
     // (envs/humanoid.py:195-206), applied where the three cotangents leave the launch
     const bool scrub = sp.sanitize != 0;
