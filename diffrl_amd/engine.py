@@ -2,8 +2,12 @@
 
 `SimStep` replaces `dflex.sim.SimulateFunc` (dflex/dflex/sim.py:2086-2154): one autograd node per
 env.step(); forward = one fused kernel launch over all substeps, backward = one fused adjoint launch.
+
+The C ABI takes bare pointers and cannot check sizes: every tensor handed to it goes through Engine._arg first.
 """
+import collections
 import ctypes as C
+import math
 
 import torch
 
@@ -28,6 +32,29 @@ class StepParameters:
     def tensors(self):
         """in the order of DSIM_PARAM_* (include/dsim.h)"""
         return tuple(getattr(self, k) for k in self.FIELDS)
+
+
+# The differentiable read-outs of a state handed in: one row per pair of C functions, names as the parameters of include/dsim.h
+# (the backward's cotangents and gradients are "g" + name; tests/test_engine_binding_cpu.py holds the rows against the header).
+#   inputs:  (name, floats per environment, optional).  Sizes are products of n (environments), nq, nd, L (links), C (contacts) and
+#            M (muscles).  An optional input may be None: "zeros" -- it counts as zeros and still has a gradient; "absent" -- it and
+#            its gradient are not there.  An input the model has no room for (M = 0) is dropped: NULL in, no gradient.
+#   outputs: (name, shape as returned[, the optional input without which it is not computed]).
+Readout = collections.namedtuple("Readout", "name forward backward inputs outputs")
+READOUTS = {r.name: r for r in (
+    Readout("body_kinematics", "dsim_body_kinematics", "dsim_body_kinematics_backward",
+            (("q", "nq", False), ("qd", "nd", "absent")),
+            (("X_sc", ("n*L", 7)), ("X_sm", ("n*L", 7)), ("v_s", ("n*L", 6), "qd"))),
+    Readout("joint_dynamics", "dsim_joint_dynamics", "dsim_joint_dynamics_backward",
+            (("q", "nq", False), ("qd", "nd", False), ("act", "nd", "zeros"), ("muscle_act", "M", "zeros")),
+            (("tau", ("n*nd",)), ("qdd", ("n*nd",)), ("f_s", ("n*L", 6)))),
+    Readout("ground_contacts", "dsim_ground_contacts", "dsim_ground_contacts_backward",
+            (("q", "nq", False), ("qd", "nd", False)),
+            (("point", ("n*C", 3)), ("vel", ("n*C", 3)), ("force", ("n*C", 3)), ("link_wrench", ("n*L", 6)))),
+    Readout("mass_matrix", "dsim_mass_matrix", "dsim_mass_matrix_backward",
+            (("q", "nq", False),),
+            (("H", ("n", "nd", "nd")), ("Hinv", ("n", "nd", "nd")), ("S", ("n*nd", 6)))),
+)}
 
 
 class Engine:
@@ -137,139 +164,142 @@ class Engine:
         definitive answer about launches still in flight."""
         self._ck(self._lib.dsim_model_status(self._h, None))
 
+    # ---- what every launch checks ----------------------------------------------------------------------
+    def _arg(self, t, numel, name, dtype=torch.float32):
+        """the one test of a tensor whose pointer goes to the library: on the model's device, of that dtype, contiguous and of
+        EXACTLY numel elements, whatever its shape (the kernels index it with the model's sizes and nothing else)"""
+        if not (torch.is_tensor(t) and t.device == self.device and t.dtype == dtype and t.is_contiguous()):
+            raise capi.DsimError("%s must be a contiguous %s tensor on %s" % (name, dtype, self.device))
+        if t.numel() != numel:
+            raise capi.DsimError("%s has %d elements, not the %d of this model and call" % (name, t.numel(), numel))
+
+    def _state(self, q, *others):
+        """n_envs as joint_q (q) gives it; every (tensor, floats per environment, name) of `others` is held to it"""
+        n = q.numel() // self.n_q if torch.is_tensor(q) else 0
+        self._arg(q, n * self.n_q, "q")
+        for t, width, name in others:
+            self._arg(t, n * width, name)
+        return n
+
+    def _sizes(self, n=1):
+        """-> the function that evaluates an entry of READOUTS, e.g. "n*L", "M" or 7, for this model and n environments"""
+        t = self.template
+        d = dict(n=n, nq=t.n_q, nd=t.n_qd, L=t.n_links, C=t.n_contacts, M=t.n_muscles)
+        return lambda dim: dim if isinstance(dim, int) else math.prod(d[k] for k in dim.split("*"))
+
+    # ---- read-outs of a state handed in (READOUTS) -----------------------------------------------------
     def body_transforms(self, q):
         """(X_sc, X_sm), each [n_envs * n_links, 7]: link frames and centre-of-mass frames in the world for the joint
         coordinates q -- the reference's State.body_X_sc / body_X_sm (dflex/dflex/model.py:338-392)."""
         q = q.detach().contiguous()
-        self._check(q, self.n_q, "joint_q")
-        n = q.numel() // self.n_q
+        n = self._state(q)
         L = self.template.n_links
         xsc = self._new(n * L, 7)
         xsm = self._new(n * L, 7)
         self._call(self._lib.dsim_body_transforms, self._h, n, _ptr(q), _ptr(xsc), _ptr(xsm))
         return xsc, xsm
 
+    def _readout_inputs(self, r, inputs):
+        """-> (n_envs, the inputs as they go to the library: checked, the ones the model has no room for dropped)"""
+        if len(inputs) != len(r.inputs):
+            raise capi.DsimError("%s takes %d inputs" % (r.forward, len(r.inputs)))
+        width = self._sizes()
+        kept = [t if width(w) else None for t, (_, w, _) in zip(inputs, r.inputs)]
+        for t, (name, w, optional) in zip(kept, r.inputs):
+            if t is None and width(w) and not optional:
+                raise capi.DsimError("%s: %s is not optional" % (r.forward, name))
+        n = self._state(kept[0], *[(t, width(w), name) for t, (name, w, _) in zip(kept[1:], r.inputs[1:]) if t is not None])
+        return n, kept
+
+    def readout_forward(self, r, *inputs):
+        """r.forward on detached contiguous tensors -> one tensor per r.outputs (None: not computed without its input)"""
+        n, inputs = self._readout_inputs(r, inputs)
+        size = self._sizes(n)
+        given = {name: t is not None for t, (name, _, _) in zip(inputs, r.inputs)}
+        outs = tuple(self._new(*map(size, o[1])) if len(o) == 2 or given[o[2]] else None for o in r.outputs)
+        self._call(getattr(self._lib, r.forward), self._h, n, *map(_ptr, inputs), *map(_ptr, outs))
+        return outs
+
+    def readout_backward(self, r, *args):
+        """r.backward: args = the inputs, then one cotangent per r.outputs; any cotangent may be None (= zeros, no buffer)
+        -> one flat gradient per r.inputs (None for an input that is absent or dropped)"""
+        n, inputs = self._readout_inputs(r, args[:len(r.inputs)])
+        cots = args[len(r.inputs):]
+        if len(cots) != len(r.outputs):
+            raise capi.DsimError("%s takes one cotangent (or None) for each of its %d outputs" % (r.backward, len(r.outputs)))
+        size = self._sizes(n)
+        for g, o in zip(cots, r.outputs):
+            if g is not None:
+                self._arg(g, math.prod(map(size, o[1])), "g" + o[0])
+        grads = tuple(self._new(size("n*" + w)) if size(w) and not (t is None and optional == "absent") else None
+                      for t, (_, w, optional) in zip(inputs, r.inputs))
+        self._call(getattr(self._lib, r.backward), self._h, n, *map(_ptr, inputs), *map(_ptr, cots), *map(_ptr, grads))
+        return grads
+
     def body_kinematics(self, q, qd=None):
         """(X_sc, X_sm, v_s | None): link frames, centre-of-mass frames ([n_envs * n_links, 7]) and -- if qd is given -- the
         world-frame spatial twists (w, v) of the links about the world origin ([n_envs * n_links, 6], the reference's
         State.body_v_s: the velocity of a point p of a link is v + w x p) of the joint state (q, qd) HANDED IN, differentiable in
-        q and qd (BodyKinematics below; one launch forward, one backward).  body_transforms is the detached read-back."""
-        if qd is None:
-            return BodyKinematics.apply(self, q, None) + (None,)
-        return BodyKinematics.apply(self, q, qd)
+        q and qd (ReadoutFunction below; one launch forward, one backward).  body_transforms is the detached read-back."""
+        out = ReadoutFunction.apply(self, READOUTS["body_kinematics"], q, qd)
+        return out if qd is not None else out + (None,)
 
     def body_kinematics_forward(self, q, qd=None):
         """dsim_body_kinematics on detached contiguous tensors"""
-        self._check(q, self.n_q, "joint_q")
-        n = q.numel() // self.n_q
-        if qd is not None:
-            self._check(qd, self.n_qd, "joint_qd")
-            if qd.numel() != n * self.n_qd:
-                raise capi.DsimError("state tensors disagree on the number of environments")
-        L = self.template.n_links
-        xsc = self._new(n * L, 7)
-        xsm = self._new(n * L, 7)
-        vs = self._new(n * L, 6) if qd is not None else None
-        self._call(self._lib.dsim_body_kinematics, self._h, n, _ptr(q), _ptr(qd), _ptr(xsc), _ptr(xsm), _ptr(vs))
-        return xsc, xsm, vs
+        return self.readout_forward(READOUTS["body_kinematics"], q, qd)
 
     def body_kinematics_backward(self, q, qd, gxsc, gxsm, gvs):
         """dsim_body_kinematics_backward: any cotangent may be None (= zeros, no buffer); -> (gq, gqd | None), flat"""
-        n = q.numel() // self.n_q
-        L = self.template.n_links
-        for g, cols, name in ((gxsc, 7, "gX_sc"), (gxsm, 7, "gX_sm"), (gvs, 6, "gv_s")):
-            if g is not None:
-                self._check(g, cols, name)
-                if g.numel() != n * L * cols:
-                    raise capi.DsimError("%s has the wrong size" % name)
-        gq = self._new(n * self.n_q)
-        gqd = self._new(n * self.n_qd) if qd is not None else None
-        self._call(self._lib.dsim_body_kinematics_backward, self._h, n, _ptr(q), _ptr(qd), _ptr(gxsc), _ptr(gxsm), _ptr(gvs),
-                   _ptr(gq), _ptr(gqd))
-        return gq, gqd
+        return self.readout_backward(READOUTS["body_kinematics"], q, qd, gxsc, gxsm, gvs)
 
     def joint_dynamics(self, q, qd, act=None, muscle_act=None):
         """(tau [n_envs * n_qd], qdd [n_envs * n_qd], f_s [n_envs * n_links, 6]): the generalized force applied (PD target, joint
         limits and actuation included), the joint accelerations H(q)^-1 tau and every link's own world-frame spatial force
         (inertial force minus gravity plus its ground contacts and muscles) -- the reference's State.joint_tau / joint_qdd /
-        body_f_s -- of the state and actuation HANDED IN, differentiable in all four inputs (JointDynamics below; one launch
+        body_f_s -- of the state and actuation HANDED IN, differentiable in all four inputs (ReadoutFunction below; one launch
         forward, one backward).  act / muscle_act default to zeros.  No step length enters: nothing is integrated."""
-        return JointDynamics.apply(self, q, qd, act, muscle_act)
+        return ReadoutFunction.apply(self, READOUTS["joint_dynamics"], q, qd, act, muscle_act)
 
     def joint_dynamics_forward(self, q, qd, act=None, muscle_act=None):
         """dsim_joint_dynamics on detached contiguous tensors"""
-        n = self._dyn_check(q, qd, act, muscle_act)
-        L = self.template.n_links
-        tau = self._new(n * self.n_qd)
-        qdd = self._new(n * self.n_qd)
-        fs = self._new(n * L, 6)
-        self._call(self._lib.dsim_joint_dynamics, self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(muscle_act), _ptr(tau),
-                   _ptr(qdd), _ptr(fs))
-        return tau, qdd, fs
+        return self.readout_forward(READOUTS["joint_dynamics"], q, qd, act, muscle_act)
 
     def joint_dynamics_backward(self, q, qd, act, muscle_act, gtau, gqdd, gfs):
         """dsim_joint_dynamics_backward: any cotangent may be None (= zeros, no buffer); -> (gq, gqd, gact, gmuscle_act | None), flat"""
-        n = self._dyn_check(q, qd, act, muscle_act)
-        L, M = self.template.n_links, self.template.n_muscles
-        for g, size, name in ((gtau, n * self.n_qd, "gtau"), (gqdd, n * self.n_qd, "gqdd"), (gfs, n * L * 6, "gf_s")):
-            if g is not None:
-                self._check(g, 1, name)
-                if g.numel() != size:
-                    raise capi.DsimError("%s has the wrong size" % name)
-        gq = self._new(n * self.n_q)
-        gqd = self._new(n * self.n_qd)
-        gact = self._new(n * self.n_qd)
-        gmact = self._new(n * M) if M > 0 else None
-        self._call(self._lib.dsim_joint_dynamics_backward, self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(muscle_act), _ptr(gtau),
-                   _ptr(gqdd), _ptr(gfs), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gmact))
-        return gq, gqd, gact, gmact
-
-    def _dyn_check(self, q, qd, act, muscle_act):
-        self._check(q, self.n_q, "joint_q")
-        self._check(qd, self.n_qd, "joint_qd")
-        n = q.numel() // self.n_q
-        M = self.template.n_muscles
-        for t, cols, name in ((qd, self.n_qd, "joint_qd"), (act, self.n_qd, "joint_act"), (muscle_act, M, "muscle_activation")):
-            if t is None or (t is muscle_act and M == 0):
-                continue
-            self._check(t, cols, name)
-            if t.numel() != n * cols:
-                raise capi.DsimError("state tensors disagree on the number of environments")
-        return n
+        return self.readout_backward(READOUTS["joint_dynamics"], q, qd, act, muscle_act, gtau, gqdd, gfs)
 
     def ground_contacts(self, q, qd):
         """(point [n_envs * C, 3], vel [n_envs * C, 3], force [n_envs * C, 3], link_wrench [n_envs * n_links, 6]): per ground
         contact, in model order, the point tested against the ground (point[:, 1] is the signed depth, negative = penetrating),
         its velocity and the normal-plus-friction force on it (exactly zero where the depth is >= 0), and per link the sum of
         (point x force, force) over its contacts -- the contact part of the reference's State.body_f_s -- of the state HANDED IN,
-        differentiable in q and qd (GroundContacts below; one launch forward, one backward)."""
-        return GroundContacts.apply(self, q, qd)
+        differentiable in q and qd (ReadoutFunction below; one launch forward, one backward)."""
+        return ReadoutFunction.apply(self, READOUTS["ground_contacts"], q, qd)
 
     def ground_contacts_forward(self, q, qd):
         """dsim_ground_contacts on detached contiguous tensors"""
-        n = self._dyn_check(q, qd, None, None)
-        Cn, L = self.template.n_contacts, self.template.n_links
-        point, vel, force = self._new(n * Cn, 3), self._new(n * Cn, 3), self._new(n * Cn, 3)
-        lw = self._new(n * L, 6)
-        self._call(self._lib.dsim_ground_contacts, self._h, n, _ptr(q), _ptr(qd), _ptr(point), _ptr(vel), _ptr(force), _ptr(lw))
-        return point, vel, force, lw
+        return self.readout_forward(READOUTS["ground_contacts"], q, qd)
 
     def ground_contacts_backward(self, q, qd, gpoint, gvel, gforce, glw):
         """dsim_ground_contacts_backward: any cotangent may be None (= zeros, no buffer); -> (gq, gqd), flat"""
-        n = self._dyn_check(q, qd, None, None)
-        Cn, L = self.template.n_contacts, self.template.n_links
-        for g, size, name in ((gpoint, n * Cn * 3, "gpoint"), (gvel, n * Cn * 3, "gvel"), (gforce, n * Cn * 3, "gforce"),
-                              (glw, n * L * 6, "glink_wrench")):
-            if g is not None:
-                self._check(g, 1, name)
-                if g.numel() != size:
-                    raise capi.DsimError("%s has the wrong size" % name)
-        gq = self._new(n * self.n_q)
-        gqd = self._new(n * self.n_qd)
-        self._call(self._lib.dsim_ground_contacts_backward, self._h, n, _ptr(q), _ptr(qd), _ptr(gpoint), _ptr(gvel), _ptr(gforce),
-                   _ptr(glw), _ptr(gq), _ptr(gqd))
-        return gq, gqd
+        return self.readout_backward(READOUTS["ground_contacts"], q, qd, gpoint, gvel, gforce, glw)
 
+    def mass_matrix(self, q):
+        """(H [n_envs, n_qd, n_qd], Hinv [n_envs, n_qd, n_qd], S [n_envs * n_qd, 6]): the joint-space inertia J^T M J + diag(armature)
+        that a refresh substep of q inverts (the reference's model.H is without the armature), its Gauss-Jordan inverse with the
+        bits the step and joint_dynamics use, and the world-frame motion axis of every dof (State.joint_S_s) -- of the q HANDED IN,
+        differentiable in it (ReadoutFunction below; one launch forward, one backward, which asks only for what has a cotangent)."""
+        return ReadoutFunction.apply(self, READOUTS["mass_matrix"], q)
+
+    def mass_matrix_forward(self, q):
+        """dsim_mass_matrix on a detached contiguous tensor"""
+        return self.readout_forward(READOUTS["mass_matrix"], q)
+
+    def mass_matrix_backward(self, q, gH, gHinv, gS):
+        """dsim_mass_matrix_backward: any cotangent may be None (= zeros, no buffer); -> gq, flat"""
+        return self.readout_backward(READOUTS["mass_matrix"], q, gH, gHinv, gS)[0]
+
+    # ---- the step --------------------------------------------------------------------------------------
     def last_substep_q(self, ckpt, substeps):
         """joint_q ENTERING the last substep of the step that wrote `ckpt` (the head of that substep's checkpoint row): what the
         reference's eval_rigid_fk saw when it filled the returned State's body_X_sc (sim.py:2316-2601)."""
@@ -281,133 +311,96 @@ class Engine:
         words = int(self._lib.dsim_ckpt_floats_mm(self._h, substeps, mm_freq))
         return self._new(n, words)
 
-    def mass_matrix(self, q):
-        """(H [n_envs, n_qd, n_qd], Hinv [n_envs, n_qd, n_qd], S [n_envs * n_qd, 6]): the joint-space inertia J^T M J + diag(armature)
-        that a refresh substep of q inverts (the reference's model.H is without the armature), its Gauss-Jordan inverse with the
-        bits the step and joint_dynamics use, and the world-frame motion axis of every dof (State.joint_S_s) -- of the q HANDED IN,
-        differentiable in it (MassMatrix below; one launch forward, one backward, which asks only for what has a cotangent)."""
-        return MassMatrix.apply(self, q)
-
-    def mass_matrix_forward(self, q):
-        """dsim_mass_matrix on a detached contiguous tensor"""
-        self._check(q, self.n_q, "joint_q")
-        n, nd = q.numel() // self.n_q, self.n_qd
-        H, Hinv, S = self._new(n, nd, nd), self._new(n, nd, nd), self._new(n * nd, 6)
-        self._call(self._lib.dsim_mass_matrix, self._h, n, _ptr(q), _ptr(H), _ptr(Hinv), _ptr(S))
-        return H, Hinv, S
-
-    def mass_matrix_backward(self, q, gH, gHinv, gS):
-        """dsim_mass_matrix_backward: any cotangent may be None (= zeros, no buffer); -> gq, flat"""
-        self._check(q, self.n_q, "joint_q")
-        n, nd = q.numel() // self.n_q, self.n_qd
-        for g, size, name in ((gH, n * nd * nd, "gH"), (gHinv, n * nd * nd, "gHinv"), (gS, n * nd * 6, "gS")):
-            if g is not None:
-                self._check(g, 1, name)
-                if g.numel() != size:
-                    raise capi.DsimError("%s has the wrong size" % name)
-        gq = self._new(n * self.n_q)
-        self._call(self._lib.dsim_mass_matrix_backward, self._h, n, _ptr(q), _ptr(gH), _ptr(gHinv), _ptr(gS), _ptr(gq))
-        return gq
-
-    def _check(self, t, cols, name):
-        if t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous():
-            raise capi.DsimError("%s must be a contiguous float32 tensor on %s" % (name, self.device))
-        if t.numel() % max(cols, 1) != 0:
-            raise capi.DsimError("%s has %d elements, not a multiple of %d" % (name, t.numel(), cols))
-
     def forward(self, q, qd, act, mact, dt, substeps, mm_freq, need_ckpt, keep_q_in=False):
         """keep_q_in: also copy joint_q entering the last substep out of the checkpoint (-> self.last_q_in; one small copy kernel,
         asked for by the operator boundary only: SimStep / SemiImplicitIntegrator.forward)"""
-        self._check(q, self.n_q, "joint_q")
-        self._check(qd, self.n_qd, "joint_qd")
-        self._check(act, self.n_qd, "joint_act")
-        n = q.numel() // self.n_q
-        if qd.numel() != n * self.n_qd or act.numel() != n * self.n_qd:
-            raise capi.DsimError("state tensors disagree on the number of environments")
-        if self.n_muscles:
-            self._check(mact, self.n_muscles, "muscle_activation")
-            if mact.numel() != n * self.n_muscles:
-                raise capi.DsimError("muscle_activation has the wrong size")
+        M = self.n_muscles
+        mact = mact if M else None
+        n = self._state(q, (qd, self.n_qd, "qd"), (act, self.n_qd, "act"), *([(mact, M, "muscle_act")] if M else []))
         q_out = torch.empty_like(q)
         qd_out = torch.empty_like(qd)
         ckpt = None
         if need_ckpt:
             ckpt = self._alloc_ckpt(n, substeps, mm_freq)
         self.last_q_in = None
-        self._call(self._lib.dsim_step_forward, self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(mact) if self.n_muscles else None,
+        self._call(self._lib.dsim_step_forward, self._h, n, _ptr(q), _ptr(qd), _ptr(act), _ptr(mact),
                    C.c_float(dt), substeps, mm_freq, _ptr(q_out), _ptr(qd_out), _ptr(ckpt))
         if ckpt is not None and keep_q_in:
             self.last_q_in = self.last_substep_q(ckpt, substeps)
         return q_out, qd_out, ckpt
 
     def _check_ckpt(self, ckpt, substeps, mm_freq):
-        """a checkpoint must be consumed with the geometry (substeps, mass-matrix frequency, checkpoint mode) it was written
-        with: the row stride differs otherwise and the adjoint launch would read other rows' words"""
+        """-> n_envs of the checkpoint.  It must be consumed with the geometry (substeps, mass-matrix frequency, checkpoint mode)
+        it was written with: the row stride differs otherwise and the adjoint launch would read other rows' words"""
         words = int(self._lib.dsim_ckpt_floats_mm(self._h, substeps, mm_freq))
-        if (ckpt.dim() != 2 or ckpt.shape[1] != words or ckpt.device != self.device or ckpt.dtype != torch.float32
-                or not ckpt.is_contiguous()):   # (a strided view, e.g. ckpt[::2], has the right shape and the wrong row stride)
+        if not torch.is_tensor(ckpt) or ckpt.dim() != 2 or ckpt.shape[1] != words:
             raise capi.DsimError("checkpoint of shape %s does not match this model / step geometry (%d floats per environment "
-                                 "in '%s' mode on %s, contiguous rows)" % (tuple(ckpt.shape), words, self.ckpt_mode, self.device))
+                                 "in '%s' mode)" % (tuple(getattr(ckpt, "shape", ())), words, self.ckpt_mode))
+        self._arg(ckpt, ckpt.shape[0] * words, "checkpoint")   # (a strided view, e.g. ckpt[::2], has the right shape and the wrong row stride)
+        return ckpt.shape[0]
+
+    def _actuation(self, ckpt, act, mact, substeps, mm_freq):
+        """The prologue of every step adjoint, first half: the checkpoint and the actuation it is consumed with
+        -> (n_envs, muscle_act | None: a model without muscles ignores it)"""
+        n, M = self._check_ckpt(ckpt, substeps, mm_freq), self.n_muscles
+        self._arg(act, n * self.n_qd, "act")
+        if not M:
+            return n, None
+        if mact is None:
+            raise capi.DsimError("model has muscles but muscle_act is None")
+        self._arg(mact, n * M, "muscle_act")
+        return n, mact
+
+    def _cotangents(self, n, gq_out, gqd_out, sets=None):
+        """Second half: the cotangents, made contiguous, and the gradient buffers in their leading shape
+        -> (K, gq_out, gqd_out, (gq, gqd, gact, gmuscle_act | None)).
+        sets None: one cotangent pair per environment, K = 1, flat buffers.  Otherwise K pairs in each of `sets` sets -- n_envs,
+        or 1 when all environments share them --, K as gq_out's size gives it, buffers [n_envs, K, .]."""
+        gq_out, gqd_out = (g.contiguous() if torch.is_tensor(g) else g for g in (gq_out, gqd_out))
+        K = 1
+        if sets is not None:
+            K = gq_out.numel() // (sets * self.n_q) if torch.is_tensor(gq_out) else 0
+            if K < 1:
+                raise capi.DsimError("gq_out / gqd_out must hold the same number K >= 1 of cotangent rows in each of %d sets" % sets)
+        self._arg(gq_out, (sets or n) * K * self.n_q, "gq_out")
+        self._arg(gqd_out, (sets or n) * K * self.n_qd, "gqd_out")
+        new = (lambda w: self._new(n * w)) if sets is None else (lambda w: self._new(n, K, w))
+        return K, gq_out, gqd_out, (new(self.n_q), new(self.n_qd), new(self.n_qd), new(self.n_muscles) if self.n_muscles else None)
 
     def backward(self, ckpt, act, mact, dt, substeps, mm_freq, gq_out, gqd_out, literal=False):
         """literal: dsim_step_backward_literal -- the quaternion blocks of the returned gq carry the component along the quaternion
         that the reference's literal adjoint has (one more small launch; default: the wrench form, no such component)"""
-        self._check_ckpt(ckpt, substeps, mm_freq)
-        n = ckpt.shape[0]
-        gq_out = gq_out.contiguous()
-        gqd_out = gqd_out.contiguous()
-        gq = self._new(n * self.n_q)
-        gqd = self._new(n * self.n_qd)
-        gact = self._new(n * self.n_qd)
-        gm = self._new(n * self.n_muscles) if self.n_muscles else None
+        n, mact = self._actuation(ckpt, act, mact, substeps, mm_freq)
+        _, gq_out, gqd_out, grads = self._cotangents(n, gq_out, gqd_out)
+        fn, scratch = self._lib.dsim_step_backward, ()
         if literal:
-            scratch = self._new(n, int(self._lib.dsim_literal_scratch_floats(self._h)))
-            self._call(self._lib.dsim_step_backward_literal, self._h, n, _ptr(ckpt), _ptr(act),
-                       _ptr(mact) if self.n_muscles else None, C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out),
-                       _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gm), _ptr(scratch))
-        else:
-            self._call(self._lib.dsim_step_backward, self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact) if self.n_muscles else None,
-                       C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gm))
-        return gq, gqd, gact, gm
+            fn, scratch = self._lib.dsim_step_backward_literal, (self._new(n, int(self._lib.dsim_literal_scratch_floats(self._h))),)
+        self._call(fn, self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact), C.c_float(dt), substeps, mm_freq, _ptr(gq_out),
+                   _ptr(gqd_out), *map(_ptr, grads + scratch))
+        return grads
 
     def backward_multi(self, ckpt, act, mact, dt, substeps, mm_freq, gq_out, gqd_out, shared=False):
         """dsim_step_backward_multi: K cotangent pairs per environment against one checkpoint, one launch of n_envs * K
         workgroups.  gq_out [K, n_q] / gqd_out [K, n_qd] with shared=True (one set for every environment), [n_envs, K, n_q] /
         [n_envs, K, n_qd] otherwise -> (gq_in [n_envs, K, n_q], gqd_in [n_envs, K, n_qd], gact [n_envs, K, n_qd],
         gmuscle_act [n_envs, K, M] | None); row (e, k) is what backward() returns for environment e and pair k, bit for bit."""
-        self._check_ckpt(ckpt, substeps, mm_freq)
-        n = ckpt.shape[0]
-        gq_out, gqd_out = gq_out.contiguous(), gqd_out.contiguous()
-        self._check(gq_out, self.n_q, "gq_out")
-        self._check(gqd_out, self.n_qd, "gqd_out")
-        K = gq_out.numel() // (self.n_q * (1 if shared else n))
-        if K <= 0 or gq_out.numel() != (1 if shared else n) * K * self.n_q or gqd_out.numel() != (1 if shared else n) * K * self.n_qd:
-            raise capi.DsimError("gq_out / gqd_out must hold the same number K >= 1 of cotangent rows%s"
-                                 % ("" if shared else " for each of the %d environments" % n))
-        self._check_act(act, mact, n)
-        M = self.n_muscles
-        gq = self._new(n, K, self.n_q)
-        gqd = self._new(n, K, self.n_qd)
-        gact = self._new(n, K, self.n_qd)
-        gm = self._new(n, K, M) if M else None
-        self._call(self._lib.dsim_step_backward_multi, self._h, n, K, 1 if shared else 0, _ptr(ckpt), _ptr(act),
-                   _ptr(mact) if M else None, C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd),
-                   _ptr(gact), _ptr(gm))
-        return gq, gqd, gact, gm
+        n, mact = self._actuation(ckpt, act, mact, substeps, mm_freq)
+        K, gq_out, gqd_out, grads = self._cotangents(n, gq_out, gqd_out, 1 if shared else n)
+        self._call(self._lib.dsim_step_backward_multi, self._h, n, K, 1 if shared else 0, _ptr(ckpt), _ptr(act), _ptr(mact),
+                   C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), *map(_ptr, grads))
+        return grads
 
     def step_jacobian(self, ckpt, act, mact, dt, substeps, mm_freq):
         """dsim_step_jacobian: the Jacobian of the step that wrote `ckpt`, one launch -> (J_state [n_envs, K, K], J_act
         [n_envs, K, n_qd], J_muscle [n_envs, K, M] | None) with K = n_q + n_qd: row k is the gradient of output coordinate k
         of (q_out | qd_out), the columns of J_state are (q_in | qd_in).  The derivative is the adjoint's (include/dsim.h); the
         quaternion blocks of the q_in columns are tangent."""
-        self._check_ckpt(ckpt, substeps, mm_freq)
-        n = ckpt.shape[0]
-        self._check_act(act, mact, n)
+        n, mact = self._actuation(ckpt, act, mact, substeps, mm_freq)
         K, M = self.n_q + self.n_qd, self.n_muscles
         J = self._new(n, K, K)
         Ja = self._new(n, K, self.n_qd)
         Jm = self._new(n, K, M) if M else None
-        self._call(self._lib.dsim_step_jacobian, self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact) if M else None, C.c_float(dt),
+        self._call(self._lib.dsim_step_jacobian, self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact), C.c_float(dt),
                    substeps, mm_freq, _ptr(J), _ptr(Ja), _ptr(Jm))
         return J, Ja, Jm
 
@@ -430,14 +423,11 @@ class Engine:
         sizes = (t.n_links,) * 4 + (t.n_q, 4 * t.n_contacts)
         if len(ts) != 6:
             raise capi.DsimError("set_params takes the six tensors of a StepParameters")
+        for x, size, name in zip(ts, sizes, StepParameters.FIELDS):   # (all of them before the first copy: all are set or none)
+            if x is not None:
+                self._arg(x, size, name)
         for field, (x, size) in enumerate(zip(ts, sizes)):
-            if x is None:
-                continue
-            x = x.detach()
-            self._check(x, 1, StepParameters.FIELDS[field])
-            if x.numel() != size:
-                raise capi.DsimError("%s has %d elements, the model has %d" % (StepParameters.FIELDS[field], x.numel(), size))
-            if size:
+            if x is not None and size:
                 self._call(self._lib.dsim_model_set_params, self._h, field, _ptr(x))
 
     def reset_params(self):
@@ -483,41 +473,19 @@ class Engine:
         [n_envs, C, 4] | None): the state gradients of backward(), bit for bit, and per environment the gradient terms of every
         dof for (target_ke, target_kd, target, limit_ke, limit_kd) and of every contact slot for (ke, kd, kf, mu), summed over
         the substeps.  The checkpoint is consumed under the parameter values its forward ran with."""
-        self._check_ckpt(ckpt, substeps, mm_freq)
-        n = ckpt.shape[0]
-        self._check_act(act, mact, n)
-        gq_out, gqd_out = gq_out.contiguous(), gqd_out.contiguous()
+        n, mact = self._actuation(ckpt, act, mact, substeps, mm_freq)
+        _, gq_out, gqd_out, grads = self._cotangents(n, gq_out, gqd_out)
         Cn = self.template.n_contacts
-        gq, gqd, gact = self._new(n * self.n_q), self._new(n * self.n_qd), self._new(n * self.n_qd)
-        gm = self._new(n * self.n_muscles) if self.n_muscles else None
         g_dof = self._new(n, 5, self.n_qd) if want_dof else None
         g_con = (self._new(n, Cn, 4) if Cn else torch.zeros(n, 0, 4, device=self.device)) if want_contact else None
-        self._call(self._lib.dsim_step_backward_params, self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact) if self.n_muscles else None,
-                   C.c_float(dt), substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gq), _ptr(gqd), _ptr(gact), _ptr(gm),
-                   _ptr(g_dof), _ptr(g_con))
-        return gq, gqd, gact, gm, g_dof, g_con
-
-    def _check_act(self, act, mact, n):
-        """the actuation a checkpoint of n environments is consumed with"""
-        self._check(act, self.n_qd, "joint_act")
-        if act.numel() != n * self.n_qd:
-            raise capi.DsimError("joint_act does not match the checkpoint's %d environments" % n)
-        if self.n_muscles:
-            if mact is None:
-                raise capi.DsimError("model has muscles but muscle_activation is None")
-            self._check(mact, self.n_muscles, "muscle_activation")
-            if mact.numel() != n * self.n_muscles:
-                raise capi.DsimError("muscle_activation does not match the checkpoint's %d environments" % n)
+        self._call(self._lib.dsim_step_backward_params, self._h, n, _ptr(ckpt), _ptr(act), _ptr(mact), C.c_float(dt),
+                   substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), *map(_ptr, grads + (g_dof, g_con)))
+        return grads + (g_dof, g_con)
 
     # ---- fused environment surface ------------------------------------------------------------------
     def env_forward(self, spec, q, qd, actions, dt, substeps, mm_freq, need_ckpt, episode=None):
         """-> (q_out, qd_out, obs, rew, ckpt[, obs_before_reset, done] when `episode` (an EpisodeIO) is given)"""
-        self._check(q, self.n_q, "joint_q")
-        self._check(qd, self.n_qd, "joint_qd")
-        self._check(actions, spec.n_act, "actions")
-        n = q.numel() // self.n_q
-        if qd.numel() != n * self.n_qd or actions.numel() != n * spec.n_act:
-            raise capi.DsimError("state / action tensors disagree on the number of environments")
+        n = self._state(q, (qd, self.n_qd, "qd"), (actions, spec.n_act, "actions"))
         q_out, qd_out = torch.empty_like(q), torch.empty_like(qd)
         obs = self._new(n, spec.n_obs)
         rew = self._new(n)
@@ -532,8 +500,12 @@ class Engine:
 
     def env_backward(self, spec, ckpt, actions, dt, substeps, mm_freq, gq_out, gqd_out, gobs, grew, gobs_before=None):
         """any cotangent may be None (= zeros: no fill kernels are launched for unused outputs)"""
-        self._check_ckpt(ckpt, substeps, mm_freq)
-        n = ckpt.shape[0]
+        n = self._check_ckpt(ckpt, substeps, mm_freq)
+        self._arg(actions, n * spec.n_act, "actions")
+        for g, width, name in ((gq_out, self.n_q, "gq_out"), (gqd_out, self.n_qd, "gqd_out"), (gobs, spec.n_obs, "gobs"),
+                               (grew, 1, "grew"), (gobs_before, spec.n_obs, "gobs_before_reset")):
+            if g is not None:
+                self._arg(g, n * width, name)
         gq = self._new(n * self.n_q)
         gqd = self._new(n * self.n_qd)
         ga = self._new(n, spec.n_act)
@@ -543,7 +515,7 @@ class Engine:
         return gq, gqd, ga
 
     def env_observe(self, spec, q, qd, stored_actions):
-        n = q.numel() // self.n_q
+        n = self._state(q, (qd, self.n_qd, "qd"), (stored_actions, spec.n_act, "stored_actions"))
         obs = self._new(n, spec.n_obs)
         rew = self._new(n)
         self._call(self._lib.dsim_env_observe, self._h, C.byref(spec), n, _ptr(q), _ptr(qd), _ptr(stored_actions), _ptr(obs),
@@ -564,15 +536,15 @@ class EpisodeIO:
         self.noise_q, self.noise_qd, self.noise_angle, self.seed = noise_q, noise_qd, float(noise_angle), int(seed)
 
     def bind(self, engine, n, n_obs):
-        dev = engine.device
-        for t, dt_, name in ((self.progress, torch.int64, "progress"), (self.reset_count, torch.int32, "reset_count")):
-            if t.device != dev or t.dtype != dt_ or t.numel() != n or not t.is_contiguous():
-                raise capi.DsimError("episode.%s must be a contiguous %s tensor of %d elements on %s" % (name, dt_, n, dev))
-        k = self.reset_q.shape[0]
-        for t, cols, name in ((self.reset_q, engine.n_q, "reset_q"), (self.reset_qd, engine.n_qd, "reset_qd")):
-            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != k * n * cols:
-                raise capi.DsimError("episode.%s must be a contiguous float32 [pool][n_envs][%d] tensor on %s" % (name, cols, dev))
-        done = torch.empty(n, dtype=torch.int64, device=dev)
+        engine._arg(self.progress, n, "episode.progress", torch.int64)
+        engine._arg(self.reset_count, n, "episode.reset_count", torch.int32)
+        k = self.reset_q.shape[0] if torch.is_tensor(self.reset_q) and self.reset_q.dim() else 0   # [pool][n_envs][n_q]
+        engine._arg(self.reset_q, k * n * engine.n_q, "episode.reset_q")
+        engine._arg(self.reset_qd, k * n * engine.n_qd, "episode.reset_qd")
+        for t, cols, name in ((self.noise_q, engine.n_q, "episode.noise_q"), (self.noise_qd, engine.n_qd, "episode.noise_qd")):
+            if t is not None:
+                engine._arg(t, cols, name)
+        done = torch.empty(n, dtype=torch.int64, device=engine.device)
         obs_before = engine._new(n, n_obs) if self.want_obs_before else None
         ep = capi.Episode()
         ep.progress, ep.done = self.progress.data_ptr(), done.data_ptr()
@@ -580,13 +552,53 @@ class EpisodeIO:
         ep.reset_q, ep.reset_qd, ep.reset_count = self.reset_q.data_ptr(), self.reset_qd.data_ptr(), self.reset_count.data_ptr()
         ep.reset_pool, ep.episode_length = int(k), int(self.episode_length)
         ep.height_terminate, ep.check_invalid = int(bool(self.height_terminate)), int(bool(self.check_invalid))
-        for t, cols, name in ((self.noise_q, engine.n_q, "noise_q"), (self.noise_qd, engine.n_qd, "noise_qd")):
-            if t is not None and (t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != cols):
-                raise capi.DsimError("episode.%s must be a contiguous float32 [%d] tensor on %s" % (name, cols, dev))
         ep.noise_q = self.noise_q.data_ptr() if self.noise_q is not None else None
         ep.noise_qd = self.noise_qd.data_ptr() if self.noise_qd is not None else None
         ep.noise_angle, ep.seed = self.noise_angle, self.seed & 0xFFFFFFFFFFFFFFFF
         return ep, (obs_before, done)
+
+
+class SimStep(torch.autograd.Function):
+    """(joint_q, joint_qd, joint_act, muscle_activation) -> (joint_q', joint_qd') for one env.step().  SimStepParams appends
+    the six parameter tensors to the inputs (`params`); the rest of the input handling is the same code."""
+
+    @staticmethod
+    def forward(ctx, engine, dt, substeps, mm_freq, q, qd, act, mact, *params):
+        q, qd, act = q.contiguous(), qd.contiguous(), act.contiguous()
+        mact = mact.contiguous() if mact is not None else None
+        need = any(t is not None and t.requires_grad for t in (q, qd, act, mact) + params)
+        q_out, qd_out, ckpt = engine.forward(q.detach(), qd.detach(), act.detach(),
+                                             mact.detach() if mact is not None else None, dt, substeps, mm_freq, need,
+                                             keep_q_in=True)
+        ctx.engine, ctx.dt, ctx.substeps, ctx.mm_freq = engine, dt, substeps, mm_freq
+        ctx.has_mact = mact is not None
+        ctx.shapes = (q.shape, qd.shape, act.shape, mact.shape if mact is not None else None)
+        if need:
+            ctx.save_for_backward(ckpt, act.detach(), mact.detach() if mact is not None else act.new_empty(0), *params)
+        return q_out.view(q.shape), qd_out.view(qd.shape)
+
+    @staticmethod
+    def saved(ctx, gq_out, gqd_out):
+        """-> (ckpt, act, muscle_act | None, gq_out, gqd_out) of a backward: a missing cotangent is zeros"""
+        ckpt, act, mact = ctx.saved_tensors[:3]
+        if gq_out is None:
+            gq_out = torch.zeros(ctx.shapes[0], dtype=torch.float32, device=ckpt.device)
+        if gqd_out is None:
+            gqd_out = torch.zeros(ctx.shapes[1], dtype=torch.float32, device=ckpt.device)
+        return ckpt, act, mact if ctx.has_mact else None, gq_out, gqd_out
+
+    @staticmethod
+    def grads(ctx, gq, gqd, gact, gm, *gparams):
+        """the gradients in the order and shapes of forward's inputs"""
+        return (None, None, None, None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), gact.view(ctx.shapes[2]),
+                gm.view(ctx.shapes[3]) if ctx.has_mact else None, *gparams)
+
+    @staticmethod
+    def backward(ctx, gq_out, gqd_out):
+        from .dflex import config
+        ckpt, act, mact, gq_out, gqd_out = SimStep.saved(ctx, gq_out, gqd_out)
+        return SimStep.grads(ctx, *ctx.engine.backward(ckpt, act, mact, ctx.dt, ctx.substeps, ctx.mm_freq, gq_out, gqd_out,
+                                                       literal=config.literal_quat_grad))
 
 
 class SimStepParams(torch.autograd.Function):
@@ -599,38 +611,21 @@ class SimStepParams(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine, dt, substeps, mm_freq, q, qd, act, mact, *params):
-        q, qd, act = q.contiguous(), qd.contiguous(), act.contiguous()
-        mact = mact.contiguous() if mact is not None else None
         params = tuple(p.contiguous() for p in params)
-        need = any(t is not None and t.requires_grad for t in (q, qd, act, mact) + params)
         engine.set_params(params)
-        q_out, qd_out, ckpt = engine.forward(q.detach(), qd.detach(), act.detach(),
-                                             mact.detach() if mact is not None else None, dt, substeps, mm_freq, need,
-                                             keep_q_in=True)
-        ctx.engine, ctx.dt, ctx.substeps, ctx.mm_freq = engine, dt, substeps, mm_freq
-        ctx.has_mact = mact is not None
-        ctx.shapes = (q.shape, qd.shape, act.shape, mact.shape if mact is not None else None)
-        if need:
-            ctx.save_for_backward(ckpt, act.detach(), mact.detach() if mact is not None else act.new_empty(0), *params)
-        return q_out.view(q.shape), qd_out.view(qd.shape)
+        return SimStep.forward(ctx, engine, dt, substeps, mm_freq, q, qd, act, mact, *params)
 
     @staticmethod
     def backward(ctx, gq_out, gqd_out):
-        ckpt, act, mact = ctx.saved_tensors[:3]
+        ckpt, act, mact, gq_out, gqd_out = SimStep.saved(ctx, gq_out, gqd_out)
         params = ctx.saved_tensors[3:]
         e = ctx.engine
-        if gq_out is None:
-            gq_out = torch.zeros(ctx.shapes[0], dtype=torch.float32, device=ckpt.device)
-        if gqd_out is None:
-            gqd_out = torch.zeros(ctx.shapes[1], dtype=torch.float32, device=ckpt.device)
         need = ctx.needs_input_grad[8:]
         e.set_params(params)
-        gq, gqd, gact, gm, g_dof, g_con = e.backward_params(ckpt, act, mact if ctx.has_mact else None, ctx.dt, ctx.substeps,
-                                                            ctx.mm_freq, gq_out, gqd_out, want_dof=any(need[:5]) or not need[5],
-                                                            want_contact=need[5])
+        gq, gqd, gact, gm, g_dof, g_con = e.backward_params(ckpt, act, mact, ctx.dt, ctx.substeps, ctx.mm_freq, gq_out, gqd_out,
+                                                            want_dof=any(need[:5]) or not need[5], want_contact=need[5])
         gp = [g.view(p.shape) if g is not None else None for g, p in zip(e.fold_param_grads(g_dof, g_con, need), params)]
-        return (None, None, None, None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), gact.view(ctx.shapes[2]),
-                gm.view(ctx.shapes[3]) if ctx.has_mact else None, *gp)
+        return SimStep.grads(ctx, gq, gqd, gact, gm, *gp)
 
 
 class EnvStep(torch.autograd.Function):
@@ -666,140 +661,34 @@ class EnvStep(torch.autograd.Function):
         return None, None, None, None, None, None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), ga.view(ctx.shapes[2])
 
 
-class BodyKinematics(torch.autograd.Function):
-    """(joint_q, joint_qd | None) -> (X_sc, X_sm[, v_s]): the kinematic read-out of a joint state with its adjoint
-    (dsim_body_kinematics / dsim_body_kinematics_backward); the backward launch re-runs the kinematics on the saved (q, qd).
-    The quaternion blocks of the returned joint_q gradient have no component along the quaternion, as SimStep's."""
+class ReadoutFunction(torch.autograd.Function):
+    """(a row r of READOUTS, its inputs) -> the outputs that are computed: a read-out of the state handed in with its adjoint
+    (r.forward / r.backward, e.g. dsim_joint_dynamics / dsim_joint_dynamics_backward); the backward launch re-runs the forward
+    pass on the saved inputs.  The quaternion blocks of the returned joint_q gradient have no component along the quaternion,
+    as SimStep's."""
 
     @staticmethod
-    def forward(ctx, engine, q, qd):
-        qc = q.detach().contiguous()
-        qdc = qd.detach().contiguous() if qd is not None else None
-        xsc, xsm, vs = engine.body_kinematics_forward(qc, qdc)
-        ctx.engine = engine
-        ctx.has_qd = qd is not None
-        ctx.shapes = (q.shape, qd.shape if qd is not None else None)
+    def forward(ctx, engine, r, *inputs):
+        # (an input the model has no room for -- muscle_act without muscles -- is absent from here on: no gradient either)
+        width = engine._sizes()
+        det = [t.detach().contiguous() if t is not None and width(w) else None for t, (_, w, _) in zip(inputs, r.inputs)]
+        outs = engine.readout_forward(r, *det)
+        ctx.engine, ctx.r = engine, r
+        ctx.shapes = [t.shape if d is not None else None for t, d in zip(inputs, det)]
         ctx.set_materialize_grads(False)   # an output the loss does not read costs no cotangent buffer
-        ctx.save_for_backward(qc, qdc if qdc is not None else qc.new_empty(0))
-        return (xsc, xsm, vs) if qd is not None else (xsc, xsm)
+        ctx.save_for_backward(*[d if d is not None else det[0].new_empty(0) for d in det])
+        return tuple(o for o in outs if o is not None)
 
     @staticmethod
-    def backward(ctx, gxsc, gxsm, gvs=None):
-        if gxsc is None and gxsm is None and gvs is None:
-            return None, None, None
-        q, qd = ctx.saved_tensors
-        c = lambda g: g.contiguous() if g is not None else None  # noqa: E731
-        gq, gqd = ctx.engine.body_kinematics_backward(q, qd if ctx.has_qd else None, c(gxsc), c(gxsm), c(gvs))
-        return None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]) if ctx.has_qd else None
-
-
-class JointDynamics(torch.autograd.Function):
-    """(joint_q, joint_qd, joint_act | None, muscle_activation | None) -> (tau, qdd, f_s): the dynamic read-out of a state with
-    its adjoint (dsim_joint_dynamics / dsim_joint_dynamics_backward); the backward launch re-runs the forward pass on the saved
-    inputs.  The quaternion blocks of the returned joint_q gradient have no component along the quaternion, as SimStep's."""
-
-    @staticmethod
-    def forward(ctx, engine, q, qd, act, mact):
-        M = engine.template.n_muscles
-        det = lambda t: t.detach().contiguous() if t is not None else None  # noqa: E731
-        qc, qdc, ac, mc = det(q), det(qd), det(act), det(mact) if M > 0 else None
-        tau, qdd, fs = engine.joint_dynamics_forward(qc, qdc, ac, mc)
-        ctx.engine = engine
-        ctx.has = (ac is not None, mc is not None)
-        ctx.shapes = (q.shape, qd.shape, act.shape if act is not None else None, mact.shape if mact is not None else None)
-        ctx.set_materialize_grads(False)   # an output the loss does not read costs no cotangent buffer
-        ctx.save_for_backward(qc, qdc, ac if ac is not None else qc.new_empty(0), mc if mc is not None else qc.new_empty(0))
-        return tau, qdd, fs
-
-    @staticmethod
-    def backward(ctx, gtau, gqdd, gfs):
-        if gtau is None and gqdd is None and gfs is None:
-            return None, None, None, None, None
-        q, qd, act, mact = ctx.saved_tensors
-        c = lambda g: g.contiguous() if g is not None else None  # noqa: E731
-        gq, gqd, gact, gmact = ctx.engine.joint_dynamics_backward(q, qd, act if ctx.has[0] else None, mact if ctx.has[1] else None,
-                                                                  c(gtau), c(gqdd), c(gfs))
-        return (None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), gact.view(ctx.shapes[2]) if ctx.has[0] else None,
-                gmact.view(ctx.shapes[3]) if ctx.has[1] else None)
-
-
-class GroundContacts(torch.autograd.Function):
-    """(joint_q, joint_qd) -> (point, vel, force, link_wrench): the ground-contact read-out of a state with its adjoint
-    (dsim_ground_contacts / dsim_ground_contacts_backward); the backward launch re-runs the forward pass on the saved inputs.  The
-    quaternion blocks of the returned joint_q gradient have no component along the quaternion, as SimStep's."""
-
-    @staticmethod
-    def forward(ctx, engine, q, qd):
-        qc, qdc = q.detach().contiguous(), qd.detach().contiguous()
-        out = engine.ground_contacts_forward(qc, qdc)
-        ctx.engine = engine
-        ctx.shapes = (q.shape, qd.shape)
-        ctx.set_materialize_grads(False)   # an output the loss does not read costs no cotangent buffer
-        ctx.save_for_backward(qc, qdc)
-        return out
-
-    @staticmethod
-    def backward(ctx, gpoint, gvel, gforce, glw):
-        if gpoint is None and gvel is None and gforce is None and glw is None:
-            return None, None, None
-        q, qd = ctx.saved_tensors
-        c = lambda g: g.contiguous() if g is not None and g.numel() else None  # noqa: E731
-        gq, gqd = ctx.engine.ground_contacts_backward(q, qd, c(gpoint), c(gvel), c(gforce), c(glw))
-        return None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1])
-
-
-class MassMatrix(torch.autograd.Function):
-    """joint_q -> (H, Hinv, S): the mass matrix read-out of a state with its adjoint (dsim_mass_matrix /
-    dsim_mass_matrix_backward); the backward launch re-runs the forward pass on the saved input.  The quaternion blocks of the
-    returned joint_q gradient have no component along the quaternion, as SimStep's."""
-
-    @staticmethod
-    def forward(ctx, engine, q):
-        qc = q.detach().contiguous()
-        out = engine.mass_matrix_forward(qc)
-        ctx.engine = engine
-        ctx.shape = q.shape
-        ctx.set_materialize_grads(False)   # an output the loss does not read costs no cotangent buffer
-        ctx.save_for_backward(qc)
-        return out
-
-    @staticmethod
-    def backward(ctx, gH, gHinv, gS):
-        if gH is None and gHinv is None and gS is None:
-            return None, None
-        q, = ctx.saved_tensors
-        c = lambda g: g.contiguous() if g is not None else None  # noqa: E731
-        return None, ctx.engine.mass_matrix_backward(q, c(gH), c(gHinv), c(gS)).view(ctx.shape)
-
-
-class SimStep(torch.autograd.Function):
-    """(joint_q, joint_qd, joint_act, muscle_activation) -> (joint_q', joint_qd') for one env.step()."""
-
-    @staticmethod
-    def forward(ctx, engine, dt, substeps, mm_freq, q, qd, act, mact):
-        q, qd, act = q.contiguous(), qd.contiguous(), act.contiguous()
-        mact = mact.contiguous() if mact is not None else None
-        need = any(t is not None and t.requires_grad for t in (q, qd, act, mact))
-        q_out, qd_out, ckpt = engine.forward(q.detach(), qd.detach(), act.detach(),
-                                             mact.detach() if mact is not None else None, dt, substeps, mm_freq, need,
-                                             keep_q_in=True)
-        ctx.engine, ctx.dt, ctx.substeps, ctx.mm_freq = engine, dt, substeps, mm_freq
-        ctx.has_mact = mact is not None
-        ctx.shapes = (q.shape, qd.shape, act.shape, mact.shape if mact is not None else None)
-        if need:
-            ctx.save_for_backward(ckpt, act.detach(), mact.detach() if mact is not None else act.new_empty(0))
-        return q_out.view(q.shape), qd_out.view(qd.shape)
-
-    @staticmethod
-    def backward(ctx, gq_out, gqd_out):
-        ckpt, act, mact = ctx.saved_tensors
-        e = ctx.engine
-        if gq_out is None:
-            gq_out = torch.zeros(ctx.shapes[0], dtype=torch.float32, device=ckpt.device)
-        if gqd_out is None:
-            gqd_out = torch.zeros(ctx.shapes[1], dtype=torch.float32, device=ckpt.device)
-        from .dflex import config
-        gq, gqd, gact, gm = e.backward(ckpt, act, mact if ctx.has_mact else None, ctx.dt, ctx.substeps, ctx.mm_freq,
-                                       gq_out, gqd_out, literal=config.literal_quat_grad)
-        return (None, None, None, None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), gact.view(ctx.shapes[2]),
-                gm.view(ctx.shapes[3]) if ctx.has_mact else None)
+    def backward(ctx, *cots):
+        if all(g is None for g in cots):
+            return (None,) * (2 + len(ctx.shapes))
+        inputs = [t if s is not None else None for t, s in zip(ctx.saved_tensors, ctx.shapes)]
+        # (an output that was not computed has no cotangent; neither has one without elements: contacts of a model without any)
+        cots = [g.contiguous() if g is not None and g.numel() else None for g in cots] + [None] * (len(ctx.r.outputs) - len(cots))
+        # Through the public <name>_backward, not readout_backward(r, ...): that method is the seam a caller observes the adjoint
+        # launch at -- the GPU tests of the four read-outs wrap it on the instance to see which cotangents autograd hands over --
+        # as it was with the four autograd classes.  (mass_matrix_backward returns its one gradient bare.)
+        grads = getattr(ctx.engine, ctx.r.name + "_backward")(*inputs, *cots)
+        grads = grads if isinstance(grads, tuple) else (grads,)
+        return (None, None) + tuple(g.view(s) if s is not None else None for g, s in zip(grads, ctx.shapes))
