@@ -147,6 +147,9 @@ ABI = {
     "dsim_step_jacobian": (_int, [_vp, _int] + [_vp] * 3 + _step + [_vp] * 4),
     "dsim_model_set_params": (_int, [_vp, _int, _vp, _vp]),
     "dsim_step_backward_params": (_int, [_vp, _int] + [_vp] * 3 + _step + [_vp] * 9),
+    "dsim_model_reserve_env_params": (_int, [_vp, _int, _vp]),
+    "dsim_model_env_params": (_int, [_vp]),
+    "dsim_model_set_env_params": (_int, [_vp, _int, _int, _vp, _vp]),
 }
 EXPORTS = tuple(ABI)
 # DSIM_PARAM_* of include/dsim.h, in the order Engine.set_params walks the fields of a StepParameters

@@ -776,6 +776,9 @@ template <class O, class D> struct KCommonT {
     float h;
     int substeps, mm_freq, n_envs;
     long long ckpt_stride;  // floats per environment (dsim_ckpt_words)
+    // 32-bit words between the constant blocks of two environments: 0 -- ONE block shared by all of them -- or the row length of
+    // the model's per-environment block (dsim_model_reserve_env_params), whose row e is then environment e's constants
+    long long cblob_stride;
     int* status;            // the model's two status words (host memory mapped into the device): dsim_check_unit_quats
 };
 
@@ -834,12 +837,16 @@ template <int MODE> __device__ __forceinline__ int dsim_env_index() {
 // context of this workgroup's environment; the executor gets the image description and loads it in begin().
 // A pair shares ONE copy of the model constants (Ant: 1096 of the forward image's 2332 words; each half loads it, same values
 // to the same words, so that a half without an environment -- odd n_envs -- may leave at once): [constants | work 0 | work 1].
+// e: the environment, which picks its row of a per-environment constant block (KCommonT::cblob_stride; 0: the one shared block,
+// the same address for every e).  The two halves of a pair cannot have rows of their own, so a model in per-environment mode
+// never launches the pair kernels (dsim_model::mode) and they keep the unstrided pointer.
 template <bool LEAN, int MODE, class Exec, class O, class D>
-__device__ __forceinline__ DsimCtxT<O, D, LEAN> start_env(float* lds, const KCommonT<O, D>& k, int image_words, Exec& ex) {
+__device__ __forceinline__ DsimCtxT<O, D, LEAN> start_env(float* lds, const KCommonT<O, D>& k, int image_words, Exec& ex, int e) {
     float* base = MODE == DSIM_MODE_PAIR ? lds + (threadIdx.x >> 5) * (image_words - k.o.const_words) : lds;
     ex.img_.lds = lds;
     ex.img_.work = base;
-    ex.img_.cblob = k.cblob;
+    if constexpr (MODE == DSIM_MODE_PAIR) ex.img_.cblob = k.cblob;
+    else ex.img_.cblob = k.cblob + (long long)e * k.cblob_stride;
     ex.img_.const_words = k.o.const_words;
     ex.img_.image_words = image_words;
     DsimCtxT<O, D, LEAN> c;
@@ -861,7 +868,7 @@ __global__ __launch_bounds__((DSIM_NL * NW * (MODE == 1 ? 2 : 1)), (MODE == DSIM
     const int e = dsim_env_index<MODE>();
     if (e >= k.n_envs) return;
     DevExec<NW, dsim_pf_regs<O, NW, LEAN, MODE>(), dsim_const_words<O>(), MODE == 1, MODE == 2 ? 2 : 1> ex;
-    auto c = start_env<LEAN, MODE>(lds, k, k.o.fwd_words, ex);
+    auto c = start_env<LEAN, MODE>(lds, k, k.o.fwd_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd, M = k.d.M;
     dsim_sim_step_forward(c, ex, k.substeps, k.mm_freq, q_in + e * nq, qd_in + e * nd, act + e * nd,
                           M ? mact + e * M : nullptr, q_out + e * nq, qd_out + e * nd,
@@ -879,7 +886,7 @@ __global__ __launch_bounds__((DSIM_NL * NW * (MODE == 1 ? 2 : 1)), DSIM_WIDE_WAV
     const int e = dsim_env_index<MODE>();
     if (e >= k.n_envs) return;
     DevExec<NW, dsim_pf_regs<O, NW, LEAN, MODE>(), dsim_const_words<O>(), MODE == 1, MODE == 2 ? 2 : 1> ex;
-    auto c = start_env<LEAN, MODE>(lds, k, k.o.total_words, ex);
+    auto c = start_env<LEAN, MODE>(lds, k, k.o.total_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd, M = k.d.M;
     dsim_sim_step_backward(c, ex, k.substeps, k.mm_freq, ckpt + (size_t)e * k.ckpt_stride, act + e * nd,
                            M ? mact + e * M : nullptr, gq_out + e * nq, gqd_out + e * nd, gq_in + e * nq,
@@ -895,8 +902,8 @@ __global__ __launch_bounds__((DSIM_NL * NW), DSIM_WIDE_WAVES(NW)) void dsim_bwd_
     extern __shared__ __attribute__((aligned(16))) float lds[];
     if ((long long)blockIdx.x >= (long long)k.n_envs * a.n_cot) return;
     DevExec<NW, dsim_pf_regs<O, NW, LEAN, DSIM_MODE_PLAIN>(), dsim_const_words<O>(), false, 1> ex;
-    auto c = start_env<LEAN, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
     const DsimMultiSlot s = dsim_multi_slot(a, (int)blockIdx.x, k.d.nd, k.d.M);
+    auto c = start_env<LEAN, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex, s.env);   // (the constants of the ENVIRONMENT, not of the workgroup)
     dsim_sim_step_backward(c, ex, k.substeps, k.mm_freq, s.ckpt, s.act, s.mact, s.gq_out, s.gqd_out, s.gq_in, s.gqd_in, s.gact,
                            s.gmact);
 }
@@ -916,7 +923,7 @@ __global__ __launch_bounds__((DSIM_NL * NW), DSIM_WIDE_WAVES(NW)) void dsim_bwd_
     if (e >= k.n_envs) return;
     DevExec<NW, dsim_pf_regs<O, NW, LEAN, DSIM_MODE_PLAIN>(), dsim_const_words<O>(), false, 1> ex;
     DsimParCtxT<O, D, LEAN> c;
-    static_cast<DsimCtxT<O, D, LEAN>&>(c) = start_env<LEAN, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    static_cast<DsimCtxT<O, D, LEAN>&>(c) = start_env<LEAN, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd, M = k.d.M, C = k.d.C;
     c.pg = lds + k.o.total_words;
     c.g_dof = a.g_dof ? a.g_dof + e * 5 * nd : nullptr;
@@ -937,7 +944,7 @@ __global__ __launch_bounds__(64) void dsim_literal_radial_kernel(KCommonT<DsimOf
     const int e = t / L, i = t - e * L;
     if (e >= k.n_envs) return;
     dsim_lit::Consts c;
-    c.cb = k.cblob;
+    c.cb = k.cblob + (long long)e * k.cblob_stride;
     c.o = k.o;
     c.d = k.d;
     const int type = c.I(k.o.jtype, i);
@@ -963,7 +970,7 @@ __global__ __launch_bounds__((DSIM_NL * NW * (MODE == 1 ? 2 : 1)), (MODE == DSIM
     const int e = dsim_env_index<MODE>();
     if (e >= k.n_envs) return;
     DevExec<NW, dsim_pf_regs<O, NW, LEAN, MODE>(), dsim_const_words<O>(), MODE == 1, MODE == 2 ? 2 : 1> ex;
-    auto c = start_env<LEAN, MODE>(lds, k, k.o.fwd_words, ex);
+    auto c = start_env<LEAN, MODE>(lds, k, k.o.fwd_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd;
     dsim_env_fused_forward(c, ex, sp, k.substeps, k.mm_freq, q_in + e * nq, qd_in + e * nd, actions + (size_t)e * sp.n_act,
                            q_out + e * nq, qd_out + e * nd, obs + (size_t)e * sp.n_obs, rew + e,
@@ -984,7 +991,7 @@ __global__ __launch_bounds__((DSIM_NL * NW * (MODE == 1 ? 2 : 1)), DSIM_WIDE_WAV
     const int e = dsim_env_index<MODE>();
     if (e >= k.n_envs) return;
     DevExec<NW, dsim_pf_regs<O, NW, LEAN, MODE>(), dsim_const_words<O>(), MODE == 1, MODE == 2 ? 2 : 1> ex;
-    auto c = start_env<LEAN, MODE>(lds, k, k.o.total_words, ex);
+    auto c = start_env<LEAN, MODE>(lds, k, k.o.total_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd;
     dsim_env_fused_backward(c, ex, sp, k.substeps, k.mm_freq, ckpt + (size_t)e * k.ckpt_stride,
                             actions + (size_t)e * sp.n_act, gq_out ? gq_out + e * nq : nullptr,
@@ -1023,7 +1030,7 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_body_kin_kernel(KCommonT<O,
     const int e = blockIdx.x;
     if (e >= k.n_envs) return;
     DevExec<NW, 6, dsim_const_words<O>(), false> ex;
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex);
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex, e);
     const size_t L = k.d.L;
     dsim_body_kin_forward(c, ex, q + (size_t)e * k.d.nq, qd ? qd + (size_t)e * k.d.nd : nullptr, xsc + e * 7 * L,
                           xsm ? xsm + e * 7 * L : nullptr, vs ? vs + e * 6 * L : nullptr, k.status, e);
@@ -1038,7 +1045,7 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_body_kin_bwd_kernel(KCommon
     const int e = blockIdx.x;
     if (e >= k.n_envs) return;
     DevExec<NW, 6, dsim_const_words<O>(), false> ex;
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex, e);
     const size_t L = k.d.L;
     dsim_body_kin_backward(c, ex, q + (size_t)e * k.d.nq, qd ? qd + (size_t)e * k.d.nd : nullptr, gxsc ? gxsc + e * 7 * L : nullptr,
                            gxsm ? gxsm + e * 7 * L : nullptr, gvs ? gvs + e * 6 * L : nullptr, gq + (size_t)e * k.d.nq,
@@ -1057,7 +1064,7 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_joint_dyn_kernel(KCommonT<O
     const int e = blockIdx.x;
     if (e >= k.n_envs) return;
     DevExec<NW, 6, dsim_const_words<O>(), false> ex;
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex);
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd, M = k.d.M, L = k.d.L;
     dsim_joint_dyn_forward(c, ex, q + e * nq, qd + e * nd, act ? act + e * nd : nullptr, (mact && M) ? mact + e * M : nullptr,
                            tau ? tau + e * nd : nullptr, qdd ? qdd + e * nd : nullptr, fs ? fs + e * 6 * L : nullptr, k.status, e);
@@ -1073,7 +1080,7 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_joint_dyn_bwd_kernel(KCommo
     const int e = blockIdx.x;
     if (e >= k.n_envs) return;
     DevExec<NW, 6, dsim_const_words<O>(), false> ex;
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd, M = k.d.M, L = k.d.L;
     dsim_joint_dyn_backward(c, ex, q + e * nq, qd + e * nd, act ? act + e * nd : nullptr, (mact && M) ? mact + e * M : nullptr,
                             gtau ? gtau + e * nd : nullptr, gqdd ? gqdd + e * nd : nullptr, gfs ? gfs + e * 6 * L : nullptr,
@@ -1091,7 +1098,7 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_ground_con_kernel(KCommonT<
     const int e = blockIdx.x;
     if (e >= k.n_envs) return;
     DevExec<NW, 6, dsim_const_words<O>(), false> ex;
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex);
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd, C = k.d.C, L = k.d.L;
     dsim_ground_contact_forward(c, ex, q + e * nq, qd + e * nd, point ? point + e * 3 * C : nullptr, vel ? vel + e * 3 * C : nullptr,
                                 force ? force + e * 3 * C : nullptr, lw ? lw + e * 6 * L : nullptr, k.status, e);
@@ -1106,7 +1113,7 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_ground_con_bwd_kernel(KComm
     const int e = blockIdx.x;
     if (e >= k.n_envs) return;
     DevExec<NW, 6, dsim_const_words<O>(), false> ex;
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd, C = k.d.C, L = k.d.L;
     dsim_ground_contact_backward(c, ex, q + e * nq, qd + e * nd, gpoint ? gpoint + e * 3 * C : nullptr,
                                  gvel ? gvel + e * 3 * C : nullptr, gforce ? gforce + e * 3 * C : nullptr,
@@ -1124,7 +1131,7 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_mass_kernel(KCommonT<O, D> 
     const int e = blockIdx.x;
     if (e >= k.n_envs) return;
     DevExec<NW, 6, dsim_const_words<O>(), false> ex;
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex);
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.fwd_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd;
     dsim_mass_forward(c, ex, q + e * nq, H ? H + e * nd * nd : nullptr, Hinv ? Hinv + e * nd * nd : nullptr,
                       S ? S + e * 6 * nd : nullptr, k.status, e);
@@ -1138,12 +1145,36 @@ __global__ __launch_bounds__(DSIM_NL * NW) void dsim_mass_bwd_kernel(KCommonT<O,
     const int e = blockIdx.x;
     if (e >= k.n_envs) return;
     DevExec<NW, 6, dsim_const_words<O>(), false> ex;
-    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex);
+    auto c = start_env<false, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex, e);
     const size_t nq = k.d.nq, nd = k.d.nd;
     dsim_mass_backward(c, ex, q + e * nq, gH ? gH + e * nd * nd : nullptr, gHinv ? gHinv + e * nd * nd : nullptr,
                        gS ? gS + e * 6 * nd : nullptr, gq + e * nq);
 }
 
+
+// The per-environment constant block (dsim_model_reserve_env_params): [rows][row_words] 32-bit words, row_words a multiple of 4 and
+// every row 16-byte aligned, as DsimImage fetches it.
+// Fill: row blockIdx.x <- the shared block, 16 bytes per lane and copy.
+__global__ __launch_bounds__(64) void dsim_env_params_fill_kernel(const uint32_t* __restrict__ shared, uint32_t* rows, int row_words,
+                                                                   int n_rows) {
+    typedef float v4f __attribute__((ext_vector_type(4)));
+    const int r = (int)blockIdx.x;
+    if (r >= n_rows) return;
+    const v4f* src = reinterpret_cast<const v4f*>(shared);
+    v4f* dst = reinterpret_cast<v4f*>(rows + (size_t)r * (size_t)row_words);
+    for (int i = (int)threadIdx.x; i < row_words / 4; i += (int)blockDim.x) dst[i] = src[i];
+}
+// Scatter: words [off, off + n) of row r <- values[r * src_stride + (0 .. n - 1)] for r < n_rows; src_stride 0 broadcasts one
+// array into every row (dsim_model_set_params in per-environment mode).  blocks_per_row workgroups of 64 lanes per row,
+// consecutive lanes on consecutive words of it.
+__global__ __launch_bounds__(64) void dsim_env_params_scatter_kernel(const float* __restrict__ values, long long src_stride,
+                                                                      uint32_t* rows, int row_words, int off, int n, int n_rows,
+                                                                      int blocks_per_row) {
+    const int r = (int)(blockIdx.x / (unsigned)blocks_per_row);
+    const int j = (int)(blockIdx.x - (unsigned)r * (unsigned)blocks_per_row) * 64 + (int)threadIdx.x;
+    if (r >= n_rows || j >= n) return;
+    reinterpret_cast<float*>(rows)[(size_t)r * (size_t)row_words + (size_t)(off + j)] = values[(size_t)r * (size_t)src_stride + (size_t)j];
+}
 
 thread_local std::string g_err;
 
@@ -1182,6 +1213,12 @@ struct dsim_model {
     DsimLayout lay;
     uint32_t* d_cblob = nullptr;
     float* d_eye = nullptr;   // (n_q + n_qd)-square identity: the seed rows of dsim_step_jacobian
+    // Per-environment mode (dsim_model_reserve_env_params): env_rows > 0 rows of env_words() words, row e the constant block of
+    // environment e; every launch then reads d_env_cblob with that stride instead of d_cblob (make_k).  d_cblob stays what
+    // dsim_model_set_params last wrote: the values "for all environments" that a new reservation starts from.
+    uint32_t* d_env_cblob = nullptr;
+    int env_rows = 0;
+    int env_words() const { return ((int)lay.cblob.size() + 3) & ~3; }
     int variant = V_GENERIC;
     int waves = 1;   // wavefronts per environment: 1 or DSIM_WAVES_WIDE
     int lean = 0;    // checkpoint mode (dsim_model_set_ckpt_mode)
@@ -1202,9 +1239,10 @@ struct dsim_model {
     // longer than a plain one (items beyond 32 lanes take two passes) and carries two environments: half the waves per launch,
     // and a third more environments resident per CU (Ant: 16 instead of 12).  DSIM_PAIR=0 / 1 forces the choice (A/B runs).
     int pair_min_envs = 1 << 30;
+    // (never in per-environment mode: a pair shares ONE copy of the constants between its two environments -- start_env)
     int mode(int n_envs, bool fwd) const {
         if (helper_ok(n_envs)) return DSIM_MODE_HELPER;
-        if (!fwd) return DSIM_MODE_PLAIN;
+        if (!fwd || env_rows) return DSIM_MODE_PLAIN;
         return n_envs >= pair_min_envs ? DSIM_MODE_PAIR : DSIM_MODE_PLAIN;
     }
 };
@@ -1253,7 +1291,8 @@ KCommonT<O, D> make_k(const dsim_model* m, O o, D d, int n_envs, float dt, int s
     KCommonT<O, D> k;
     k.o = o;
     k.d = d;
-    k.cblob = m->d_cblob;
+    k.cblob = m->env_rows ? m->d_env_cblob : m->d_cblob;
+    k.cblob_stride = m->env_rows ? m->env_words() : 0;
     k.h = dt / float(substeps);
     k.substeps = substeps;
     k.mm_freq = mm_freq;
@@ -1296,6 +1335,9 @@ int check_common(const dsim_model* m, int n_envs, float dt, int substeps, int mm
     if (int rc = check_device(m)) return rc;
     if (int rc = check_status(m)) return rc;
     if (n_envs <= 0) return fail(DSIM_ERR_INVALID, "n_envs must be positive");
+    if (m->env_rows && n_envs > m->env_rows)
+        return fail(DSIM_ERR_INVALID, "n_envs = " + std::to_string(n_envs) + " but the model holds per-environment parameters for " +
+                                          std::to_string(m->env_rows) + " environments (dsim_model_reserve_env_params)");
     if (substeps <= 0 || mm_freq <= 0) return fail(DSIM_ERR_INVALID, "substeps and mm_freq must be positive");
     if (!(dt > 0.f)) return fail(DSIM_ERR_INVALID, "dt must be positive");
     return DSIM_OK;
@@ -1434,6 +1476,7 @@ template <class Fam, class... Args> int launch_readout(const dsim_model* m, int 
 // the model's device / host allocations and the model itself (a model whose creation failed half-way included)
 void free_model(dsim_model* m) {
     if (m->d_cblob) (void)hipFree(m->d_cblob);
+    if (m->d_env_cblob) (void)hipFree(m->d_env_cblob);
     if (m->d_eye) (void)hipFree(m->d_eye);
     if (m->h_status) (void)hipHostFree(const_cast<int*>(m->h_status));
     delete m;
@@ -1703,28 +1746,102 @@ int dsim_step_jacobian(const dsim_model* m, int n_envs, const float* ckpt, const
     return step_backward_multi(m, n_envs, dt, substeps, mm_freq, a, hip_stream);
 }
 
+// where a parameter array lies in the constant block: (word offset, floats), or false for an unknown field
+static bool param_field(const dsim_model* m, int field, int& off, int& n) {
+    const DsimOff& o = m->lay.o;
+    const DsimDims& d = m->lay.d;
+    switch (field) {
+    case DSIM_PARAM_TARGET_KE: off = o.tke; n = d.L; return true;
+    case DSIM_PARAM_TARGET_KD: off = o.tkd; n = d.L; return true;
+    case DSIM_PARAM_LIMIT_KE: off = o.lke; n = d.L; return true;
+    case DSIM_PARAM_LIMIT_KD: off = o.lkd; n = d.L; return true;
+    case DSIM_PARAM_TARGET: off = o.target; n = d.nq; return true;
+    case DSIM_PARAM_CONTACT_MATERIAL: off = o.cmat; n = 4 * d.C; return true;
+    default: return false;
+    }
+}
+
+// ONE launch: words [off, off + n) of rows 0 .. n_rows - 1 of the per-environment block <- values (src_stride floats apart; 0: the
+// same array into every row).  The rows exist (n_rows <= env_rows) and [off, off + n) lies inside a row (param_field).
+static int scatter_env_params(dsim_model* m, int off, int n, int n_rows, const float* values, long long src_stride, void* hip_stream) {
+    const int bpr = (n + 63) / 64;
+    hipLaunchKernelGGL(dsim_env_params_scatter_kernel, dim3((unsigned)((long long)n_rows * bpr)), dim3(64), 0,
+                       static_cast<hipStream_t>(hip_stream), values, src_stride, m->d_env_cblob, m->env_words(), off, n, n_rows, bpr);
+    return launched("launch dsim_env_params_scatter_kernel");
+}
+
 int dsim_model_set_params(dsim_model* m, int field, const float* dev_values, void* hip_stream) {
     if (!m) return fail(DSIM_ERR_INVALID, "null model");
     if (!dev_values) return fail(DSIM_ERR_INVALID, "null pointer (dev_values)");
-    const DsimOff& o = m->lay.o;
-    const DsimDims& d = m->lay.d;
     int off = 0, n = 0;
-    switch (field) {
-    case DSIM_PARAM_TARGET_KE: off = o.tke; n = d.L; break;
-    case DSIM_PARAM_TARGET_KD: off = o.tkd; n = d.L; break;
-    case DSIM_PARAM_LIMIT_KE: off = o.lke; n = d.L; break;
-    case DSIM_PARAM_LIMIT_KD: off = o.lkd; n = d.L; break;
-    case DSIM_PARAM_TARGET: off = o.target; n = d.nq; break;
-    case DSIM_PARAM_CONTACT_MATERIAL: off = o.cmat; n = 4 * d.C; break;
-    default: return fail(DSIM_ERR_INVALID, "unknown parameter field " + std::to_string(field));
-    }
+    if (!param_field(m, field, off, n)) return fail(DSIM_ERR_INVALID, "unknown parameter field " + std::to_string(field));
     if (int rc = check_device(m)) return rc;
     if (n == 0) return DSIM_OK;   // (contact materials of a model without contacts)
     // the six arrays are plain copies in the constant block (dsim_layout.hpp: put_f); nothing on the host is derived from them
     hipError_t e = hipMemcpyAsync(m->d_cblob + off, dev_values, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice,
                                   static_cast<hipStream_t>(hip_stream));
     if (e != hipSuccess) return hip_fail(e, "dsim_model_set_params");
+    // per-environment mode: "for ALL environments" is every reserved row as well
+    if (m->env_rows) return scatter_env_params(m, off, n, m->env_rows, dev_values, 0, hip_stream);
     return DSIM_OK;
+}
+
+int dsim_model_env_params(const dsim_model* m) { return m ? m->env_rows : 0; }
+
+int dsim_model_reserve_env_params(dsim_model* m, int n_envs, void* hip_stream) {
+    if (!m) return fail(DSIM_ERR_INVALID, "null model");
+    if (n_envs < 0) return fail(DSIM_ERR_INVALID, "n_envs must not be negative");
+    if (int rc = check_device(m)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    // it allocates and frees: not something a captured graph can replay
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    hipError_t e = hipStreamIsCapturing(st, &cap);
+    if (e != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        if (e != hipSuccess) (void)hipGetLastError();
+        return fail(DSIM_ERR_INVALID, "dsim_model_reserve_env_params allocates device memory and cannot run while a stream capture is "
+                                      "active: reserve before the capture begins");
+    }
+    if (n_envs != m->env_rows && m->d_env_cblob) {   // (hipFree waits for the launches that still read the rows)
+        uint32_t* old = m->d_env_cblob;
+        m->d_env_cblob = nullptr;
+        m->env_rows = 0;
+        e = hipFree(old);
+        if (e != hipSuccess) return hip_fail(e, "dsim_model_reserve_env_params (hipFree)");
+    }
+    if (n_envs == 0) return DSIM_OK;
+    const int W = m->env_words();
+    if (!m->d_env_cblob) {
+        e = hipMalloc(&m->d_env_cblob, sizeof(uint32_t) * (size_t)W * (size_t)n_envs);
+        if (e != hipSuccess) {
+            m->d_env_cblob = nullptr;
+            return hip_fail(e, "dsim_model_reserve_env_params (hipMalloc)");
+        }
+    }
+    hipLaunchKernelGGL(dsim_env_params_fill_kernel, dim3((unsigned)n_envs), dim3(64), 0, st, m->d_cblob, m->d_env_cblob, W, n_envs);
+    if (int rc = launched("launch dsim_env_params_fill_kernel")) {
+        if (!m->env_rows) {
+            (void)hipFree(m->d_env_cblob);
+            m->d_env_cblob = nullptr;
+        }
+        return rc;
+    }
+    m->env_rows = n_envs;
+    return DSIM_OK;
+}
+
+int dsim_model_set_env_params(dsim_model* m, int field, int n_envs, const float* dev_values, void* hip_stream) {
+    if (!m) return fail(DSIM_ERR_INVALID, "null model");
+    if (!dev_values) return fail(DSIM_ERR_INVALID, "null pointer (dev_values)");
+    int off = 0, n = 0;
+    if (!param_field(m, field, off, n)) return fail(DSIM_ERR_INVALID, "unknown parameter field " + std::to_string(field));
+    if (!m->env_rows)
+        return fail(DSIM_ERR_INVALID, "the model shares one parameter block between all environments: dsim_model_reserve_env_params first");
+    if (n_envs < 1 || n_envs > m->env_rows)
+        return fail(DSIM_ERR_INVALID, "n_envs = " + std::to_string(n_envs) + " is outside 1 .. " + std::to_string(m->env_rows) +
+                                          ", the environments the model holds per-environment parameters for");
+    if (int rc = check_device(m)) return rc;
+    if (n == 0) return DSIM_OK;   // (contact materials of a model without contacts)
+    return scatter_env_params(m, off, n, n_envs, dev_values, n, hip_stream);
 }
 
 int dsim_step_backward_params(const dsim_model* m, int n_envs, const float* ckpt, const float* act, const float* muscle_act,

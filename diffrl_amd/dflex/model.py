@@ -513,12 +513,17 @@ class Model:
             mask[i, int(t.joint_qd_start[i]):int(t.joint_qd_start[i + 1])] = True
         return torch.as_tensor(mask, device=self.device)
 
-    def step_parameters(self):
+    def step_parameters(self, per_env=False):
         """The parameters a step is differentiable in, as device tensors cloned from the template and shared by all articulations
         (engine.StepParameters): joint_target_ke / joint_target_kd / joint_limit_ke / joint_limit_kd [links_per_articulation],
         joint_target [coords_per_articulation], contact_material [contacts_per_articulation, 4] = (ke, kd, kf, mu) per contact
         slot.  Set requires_grad on the ones to fit and hand the object to SemiImplicitIntegrator.forward(..., params=p); tie the
-        contacts of one shape together with contact_shape.  Fresh host-to-device copies: take it once, outside a graph capture."""
+        contacts of one shape together with contact_shape.  Fresh host-to-device copies: take it once, outside a graph capture.
+        per_env: a value per articulation instead (engine.EnvStepParameters) -- the same six tensors with a leading dimension of
+        articulation_count, every row the template's values; the integrator then runs articulation e under row e and returns
+        row-wise gradients."""
+        if per_env:
+            return self.engine().env_step_parameters(self.articulation_count)
         return self.engine().step_parameters()
 
     @property

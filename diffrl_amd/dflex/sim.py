@@ -6,7 +6,7 @@ launch), instead of ~100 kernel launches + ~280 tensor allocations per step in t
 (SURVEY.md section 3.2)."""
 import torch
 
-from ..engine import SimStep, SimStepParams
+from ..engine import EnvStepParameters, SimStep, SimStepEnvParams, SimStepParams
 from . import config
 from .model import Model, ModelBuilder, State  # noqa: F401  (re-exported like dflex.sim)
 
@@ -20,18 +20,23 @@ class SemiImplicitIntegrator:
         materials and is differentiable in them too -- the parameter tensors that require grad receive gradients summed over the
         environments (engine.SimStepParams).  The values are SET on the model (device-to-device, on the current stream) and stay
         set: every later launch on it, the fused env steps and the read-outs included, runs under what was set last, until
-        model.engine().reset_params().  Without params: the path as it always was, under whatever the model holds."""
+        model.engine().reset_params().  Without params: the path as it always was, under whatever the model holds.
+        params = Model.step_parameters(per_env=True) (an engine.EnvStepParameters): row e of every tensor is environment e's
+        value, and a tensor that requires grad receives in row e the gradient of environment e's outputs -- nothing is summed
+        (engine.SimStepEnvParams).  The first such call reserves the model's per-environment block: make it before a graph
+        capture (Engine.set_env_params)."""
         eng = model.engine()
         mact = model.muscle_activation if model.muscle_count else None
         out = State(act_like=model.joint_qd, model=model)
         if params is not None and not config.no_grad:
             if config.literal_quat_grad:
                 raise RuntimeError("params: there is no literal-quaternion variant of the parameter adjoint (include/dsim.h)")
-            out.joint_q, out.joint_qd = SimStepParams.apply(eng, float(dt), int(substeps), int(mass_matrix_freq), state_in.joint_q,
-                                                            state_in.joint_qd, state_in.joint_act, mact, *params.tensors())
+            node = SimStepEnvParams if isinstance(params, EnvStepParameters) else SimStepParams
+            out.joint_q, out.joint_qd = node.apply(eng, float(dt), int(substeps), int(mass_matrix_freq), state_in.joint_q,
+                                                   state_in.joint_qd, state_in.joint_act, mact, *params.tensors())
         elif config.no_grad:
             if params is not None:
-                eng.set_params(params)
+                (eng.set_env_params if isinstance(params, EnvStepParameters) else eng.set_params)(params)
             with torch.no_grad():
                 q, qd, _ = eng.forward(state_in.joint_q.contiguous(), state_in.joint_qd.contiguous(),
                                        state_in.joint_act.contiguous(), mact.contiguous() if mact is not None else None,

@@ -34,6 +34,12 @@ class StepParameters:
         return tuple(getattr(self, k) for k in self.FIELDS)
 
 
+class EnvStepParameters(StepParameters):
+    """StepParameters with a value PER ENVIRONMENT: the same six fields with a leading environment dimension, joint_target_ke /
+    joint_target_kd / joint_limit_ke / joint_limit_kd [N, n_links], joint_target [N, n_q], contact_material [N, C, 4].
+    Engine.env_step_parameters(N) expands the template's values; Engine.set_env_params puts them on the model."""
+
+
 # The differentiable read-outs of a state handed in: one row per pair of C functions, names as the parameters of include/dsim.h
 # (the backward's cotangents and gradients are "g" + name; tests/test_engine_binding_cpu.py holds the rows against the header).
 #   inputs:  (name, floats per environment, optional).  Sizes are products of n (environments), nq, nd, L (links), C (contacts) and
@@ -413,6 +419,59 @@ class Engine:
                               joint_limit_ke=dev(t.joint_limit_ke, -1), joint_limit_kd=dev(t.joint_limit_kd, -1),
                               joint_target=dev(t.joint_target, -1), contact_material=dev(t.contact_material, -1, 4))
 
+    def env_step_parameters(self, n_envs):
+        """EnvStepParameters for n_envs environments: the template's values in every row, contiguous tensors of their own (fresh
+        host-to-device copies: take them once, outside a graph capture)"""
+        p = self.step_parameters()
+        return EnvStepParameters(**{k: x.unsqueeze(0).repeat(int(n_envs), *([1] * x.dim())).contiguous()
+                                    for k, x in zip(StepParameters.FIELDS, p.tensors())})
+
+    def _param_sizes(self):
+        """floats per environment of the six fields, in their order"""
+        t = self.template
+        return (t.n_links,) * 4 + (t.n_q, 4 * t.n_contacts)
+
+    def env_params(self):
+        """dsim_model_env_params: the environments the model holds parameter rows for, 0 while all share one block"""
+        return int(self._lib.dsim_model_env_params(self._h))
+
+    def reserve_env_params(self, n_envs):
+        """dsim_model_reserve_env_params: a constant block for each of n_envs environments, every row filled with the values all
+        environments share at that moment; 0: back to one shared block.  It allocates or frees device memory: not capturable
+        (refused during a graph capture).  The Engine remembers the count (its model is its own), so that set_env_params asks
+        for a reservation only when the number of environments changes."""
+        self._call(self._lib.dsim_model_reserve_env_params, self._h, int(n_envs))
+        self._env_rows = int(n_envs)
+
+    def set_env_params(self, p):
+        """dsim_model_set_env_params for every field of p (an EnvStepParameters, or its six tensors in that order; an entry may
+        be None = left as it is): row e of a tensor becomes environment e's value.  All tensors are checked before the first
+        copy and must agree on the number n of environments.  One launch per field on the current stream, capturable, no host
+        synchronisation -- EXCEPT the first call with a new n, which reserves the model's per-environment block
+        (dsim_model_reserve_env_params: it allocates, fills every row from the values all environments share at that moment,
+        and is refused during a graph capture): make that call before capturing.  From then on every launch on this model runs
+        environment e under row e, a launch of fewer environments under the first rows, and a launch of more than n is an
+        error; set_params still sets a field for ALL environments; reset_params() goes back to one shared block."""
+        ts = p.tensors() if isinstance(p, StepParameters) else tuple(p)
+        sizes = self._param_sizes()
+        if len(ts) != 6:
+            raise capi.DsimError("set_env_params takes the six tensors of an EnvStepParameters")
+        ns = {x.shape[0] for x in ts if torch.is_tensor(x) and x.dim() >= 2}
+        if len(ns) != 1 or any(x is not None and not (torch.is_tensor(x) and x.dim() >= 2) for x in ts):
+            raise capi.DsimError("set_env_params: every tensor given needs a leading environment dimension, the same for all "
+                                 "(found %s)" % sorted(ns))
+        n = ns.pop()
+        if n < 1:
+            raise capi.DsimError("set_env_params: no environments")
+        for x, size, name in zip(ts, sizes, StepParameters.FIELDS):   # (all of them before the first copy: all are set or none)
+            if x is not None:
+                self._arg(x, n * size, name)
+        if getattr(self, "_env_rows", 0) != n:
+            self.reserve_env_params(n)
+        for field, (x, size) in enumerate(zip(ts, sizes)):
+            if x is not None and size:
+                self._call(self._lib.dsim_model_set_env_params, self._h, field, n, _ptr(x))
+
     def set_params(self, p):
         """dsim_model_set_params for every field of p (a StepParameters, or its six tensors in that order; an entry may be None =
         left as it is): device-to-device copies on the current stream, capturable, no host synchronisation.  Every later launch
@@ -431,9 +490,11 @@ class Engine:
                 self._call(self._lib.dsim_model_set_params, self._h, field, _ptr(x))
 
     def reset_params(self):
-        """back to the template's values"""
+        """back to the template's values, shared by all environments (a per-environment block is released: not capturable then)"""
         if getattr(self, "_params0", None) is None:
             self._params0 = self.step_parameters()
+        if getattr(self, "_env_rows", 0):
+            self.reserve_env_params(0)
         self.set_params(self._params0)
 
     def _fold_index(self):
@@ -451,11 +512,24 @@ class Engine:
             self._fold = (mk(link), mk(dofs), mk(coords))
         return self._fold
 
-    def fold_param_grads(self, g_dof, g_contact, need=(True,) * 6):
+    def fold_param_grads(self, g_dof, g_contact, need=(True,) * 6, per_env=False):
         """what backward_params returns per environment and dof / contact slot -> the gradients of the six StepParameters tensors
         (in their order; None where not needed): summed over the environments, dofs folded into their links (a ball joint's three
-        dofs share one gain) and, for joint_target, into the coordinate of their hinge / slider"""
+        dofs share one gain) and, for joint_target, into the coordinate of their hinge / slider.
+        per_env: the environment dimension is kept -- [N, n_links], [N, n_q], [N, C, 4], the gradients of an EnvStepParameters."""
         gp = [None] * 6
+        if per_env:
+            if any(need[:5]):
+                link, dofs, coords = self._fold_index()
+                N = g_dof.shape[0]
+                for field, row in ((0, 0), (1, 1), (2, 3), (3, 4)):
+                    if need[field]:
+                        gp[field] = torch.zeros(N, self.template.n_links, device=g_dof.device).index_add_(1, link, g_dof[:, row])
+                if need[4]:
+                    gp[4] = torch.zeros(N, self.n_q, device=g_dof.device).index_add_(1, coords, g_dof[:, 2][:, dofs])
+            if need[5]:
+                gp[5] = g_contact
+            return gp
         if any(need[:5]):
             link, dofs, coords = self._fold_index()
             d = g_dof.sum(dim=0)   # [5, nd]: target_ke, target_kd, target, limit_ke, limit_kd
@@ -625,6 +699,32 @@ class SimStepParams(torch.autograd.Function):
         gq, gqd, gact, gm, g_dof, g_con = e.backward_params(ckpt, act, mact, ctx.dt, ctx.substeps, ctx.mm_freq, gq_out, gqd_out,
                                                             want_dof=any(need[:5]) or not need[5], want_contact=need[5])
         gp = [g.view(p.shape) if g is not None else None for g, p in zip(e.fold_param_grads(g_dof, g_con, need), params)]
+        return SimStep.grads(ctx, gq, gqd, gact, gm, *gp)
+
+
+class SimStepEnvParams(torch.autograd.Function):
+    """SimStepParams with a value per environment: the six tensors of an EnvStepParameters as inputs.  forward sets them on the
+    model (Engine.set_env_params), then steps; backward sets the SAVED tensors again, launches dsim_step_backward_params and folds
+    dofs into links (joint_target: into coordinates) WITHOUT summing over the environments: every row receives the gradient of
+    its own environment's outputs, in the tensor's own shape -- N parameter hypotheses differentiated by one launch."""
+
+    @staticmethod
+    def forward(ctx, engine, dt, substeps, mm_freq, q, qd, act, mact, *params):
+        params = tuple(p.contiguous() for p in params)
+        engine.set_env_params(params)
+        return SimStep.forward(ctx, engine, dt, substeps, mm_freq, q, qd, act, mact, *params)
+
+    @staticmethod
+    def backward(ctx, gq_out, gqd_out):
+        ckpt, act, mact, gq_out, gqd_out = SimStep.saved(ctx, gq_out, gqd_out)
+        params = ctx.saved_tensors[3:]
+        e = ctx.engine
+        need = ctx.needs_input_grad[8:]
+        e.set_env_params(params)
+        gq, gqd, gact, gm, g_dof, g_con = e.backward_params(ckpt, act, mact, ctx.dt, ctx.substeps, ctx.mm_freq, gq_out, gqd_out,
+                                                            want_dof=any(need[:5]) or not need[5], want_contact=need[5])
+        gp = [g.view(p.shape) if g is not None else None
+              for g, p in zip(e.fold_param_grads(g_dof, g_con, need, per_env=True), params)]
         return SimStep.grads(ctx, gq, gqd, gact, gm, *gp)
 
 

@@ -128,6 +128,41 @@ class DFlexEnv:
             self._spec_cache.sanitize_grads = int(bool(self.sanitize_grads))
         return self._spec_cache
 
+    def randomize_step_parameters(self, scale, generator=None):
+        """Domain randomisation per ENVIRONMENT: every environment gets the template's gains, targets and contact materials
+        times factors of its own, and every later env.step() runs under them -- still fused, one launch, capturable.
+        scale: {field: (lo, hi)} over the fields of engine.StepParameters, and for "contact_material" {column: (lo, hi)} with
+        column one of "ke", "kd", "kf", "mu" (or 0 .. 3); a field or column not named keeps the template's values.  For each
+        one named, ONE factor per environment is drawn uniformly from [lo, hi) on the device (generator: a torch.Generator of
+        that device) and multiplies the whole array.  -> the engine.EnvStepParameters that were set.  Call it outside a graph
+        capture (it allocates; the first call reserves the model's per-environment block); to draw again between captured steps,
+        update tensors in place and hand them to model.engine().set_env_params, which is capturable from then on.  The values
+        are not redrawn when an environment restarts inside the fused step, and the fused env adjoint returns no parameter
+        gradients (those are the integrator's: SemiImplicitIntegrator.forward(..., params=...)).  model.engine().reset_params()
+        goes back to the template's values for all environments."""
+        eng = self.model.engine()
+        p = eng.env_step_parameters(self.num_envs)
+        n, dev = self.num_envs, p.joint_target_ke.device
+
+        def factor(rng):
+            lo, hi = (float(v) for v in rng)
+            return lo + (hi - lo) * torch.rand(n, device=dev, generator=generator)
+
+        columns = ("ke", "kd", "kf", "mu")
+        for field, rng in scale.items():
+            if field not in p.FIELDS:
+                raise KeyError("randomize_step_parameters: %r is not one of %s" % (field, ", ".join(p.FIELDS)))
+            x = getattr(p, field)
+            if field == "contact_material":
+                for col, r in rng.items():
+                    j = columns.index(col) if col in columns else int(col)
+                    x[:, :, j] *= factor(r).view(n, 1)
+            else:
+                x *= factor(rng).view(n, 1)
+        eng.set_env_params(p)
+        self.step_params = p
+        return p
+
     def stored_actions(self, actions):
         """what the environment keeps as self.actions for raw policy actions (clipped, maybe remapped)"""
         return torch.clip(actions, -1.0, 1.0)

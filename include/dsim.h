@@ -271,6 +271,36 @@ int dsim_step_jacobian(const dsim_model* m, int n_envs,
 #define DSIM_PARAM_CONTACT_MATERIAL 5
 int dsim_model_set_params(dsim_model* m, int field, const float* dev_values, void* hip_stream);
 
+/* Per-environment parameter VALUES (ABI 110: functions added): one constant block per environment instead of one for all.
+ *
+ * dsim_model_reserve_env_params with n_envs = R > 0 allocates a device block [R][W] -- W the model's whole constant block rounded
+ * up to a multiple of 4 words, R * W * 4 bytes (W * 4: about 4.3 KB for Ant, 11.5 KB for Humanoid, 25.2 KB for SNUHumanoid) --,
+ * re-allocating if R differs from what is reserved, fills EVERY row from the current shared block (what the model was created
+ * with, or what dsim_model_set_params last wrote; a kernel on hip_stream) and switches the model to per-environment mode.  With
+ * n_envs = 0 it frees the block and switches back to shared mode, under the shared block's values.  It allocates and frees
+ * device memory, so it may synchronise the device, and it is NOT capturable: called while a capture is active on hip_stream it
+ * changes nothing and returns DSIM_ERR_INVALID.  Reserve once, before capturing.
+ * dsim_model_env_params returns R, or 0 in shared mode.
+ *
+ * In per-environment mode every launch on the model -- the step kernels in their plain and helper-wave launch modes, the fused
+ * env kernels, the multi-cotangent and Jacobian launch, the parameter adjoint, the read-outs, the literal launch -- runs
+ * environment e under row e: a launch of n_envs <= R environments uses the first n_envs rows, n_envs > R is DSIM_ERR_INVALID
+ * (the message names both numbers; nothing is launched).  Environment e's results are BIT FOR BIT those of a shared-mode launch
+ * under row e's values.  The two-environments-per-wavefront forward kernels share one copy of the constants between the two and
+ * are not used in this mode: launches beyond the helper-wave capacity run the plain kernels.  dsim_step_backward_params then
+ * returns per environment the gradient terms of THAT environment's values: do not sum them over the environments.
+ *
+ * dsim_model_set_env_params writes ONE parameter array of rows 0 .. n_envs - 1 from DEVICE memory: dev_values is
+ * [n_envs][n] with the field's n as in the table above, 1 <= n_envs <= R.  One kernel launch on hip_stream -- asynchronous,
+ * capturable, no host synchronisation -- with the ORDERING statement of dsim_model_set_params; rows from n_envs on keep their
+ * values.  The contact field of a model with C == 0: DSIM_OK, nothing done.  DSIM_ERR_INVALID: NULL dev_values, an unknown
+ * field, a model in shared mode, n_envs outside 1 .. R.
+ * dsim_model_set_params keeps its meaning, "for ALL environments": in per-environment mode it writes the shared block as above
+ * and broadcasts the array into every reserved row (one more launch on hip_stream, same ordering). */
+int dsim_model_reserve_env_params(dsim_model* m, int n_envs, void* hip_stream);
+int dsim_model_env_params(const dsim_model* m);
+int dsim_model_set_env_params(dsim_model* m, int field, int n_envs, const float* dev_values, void* hip_stream);
+
 /* dsim_step_backward with the gradients of those parameters: same arguments, same conventions, and gq_in, gqd_in, gact,
  * gmuscle_act equal to dsim_step_backward's BIT FOR BIT (the same arithmetic; one kernel family more, plain launch mode).
  * Two more outputs, both WRITTEN (not accumulated), either may be NULL but not both (DSIM_ERR_INVALID):
