@@ -150,6 +150,7 @@ ABI = {
     "dsim_model_reserve_env_params": (_int, [_vp, _int, _vp]),
     "dsim_model_env_params": (_int, [_vp]),
     "dsim_model_set_env_params": (_int, [_vp, _int, _int, _vp, _vp]),
+    "dsim_env_step_backward_params": (_int, [_vp, _spec, _int] + [_vp] * 2 + _step + [_vp] * 11),
 }
 EXPORTS = tuple(ABI)
 # DSIM_PARAM_* of include/dsim.h, in the order Engine.set_params walks the fields of a StepParameters

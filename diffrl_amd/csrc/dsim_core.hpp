@@ -99,6 +99,26 @@ DSIM_FN void dsim_par_dof(const Ctx& c, int d, bool hinge, bool ball, float q, f
         }
     }
 }
+// The two ends of the accumulators, stated once for both drivers of the reverse sweep (dsim_sim_step_backward,
+// dsim_env_fused_backward); with any other context they are empty.  Zeroing: where the driver loads its cotangents.
+template <int NL, class Ctx> DSIM_FN void dsim_par_zero(const Ctx& c, int lane) {
+    if constexpr (DsimParamGrad<Ctx>::value)
+        for (int k = lane; k < dsim_par_words(c.d.nd, c.d.C); k += NL) c.pg[k] = 0.f;
+}
+// Storing: per dof [5][nd] and per contact [C][4], summed over the substeps; written, every word by one lane.  `put` is what the
+// driver does to a value that leaves the launch (the fused env adjoint: its nan_to_num scrub).
+template <int NL, class Ctx, class Put> DSIM_FN void dsim_par_store(const Ctx& c, int lane, Put&& put) {
+    if constexpr (DsimParamGrad<Ctx>::value) {
+        const int nd = c.d.nd;
+        if (c.g_dof)
+            for (int it = lane; it < 5 * nd; it += NL) {
+                const int j = it / nd, d = it - nd * j;
+                c.g_dof[it] = put(c.pg[5 * d + j]);
+            }
+        if (c.g_contact)
+            for (int k = lane; k < 4 * c.d.C; k += NL) c.g_contact[k] = put(c.pg[5 * nd + k]);
+    }
+}
 // words of one substep's checkpoint row: the saved block (everything the adjoint reads) or, in the lean mode, only (q, qd)
 template <class Ctx> DSIM_FN int dsim_row(const Ctx& c) { return Ctx::LEAN ? c.o.xsc - c.o.q : c.o.save_words; }
 
@@ -4918,8 +4938,7 @@ DSIM_FN void dsim_sim_step_backward(const Ctx& c, Exec& ex, int substeps, int mm
             WF(mact)[k] = g_mact[k];
             WF(amact)[k] = 0.f;
         }
-        if constexpr (DsimParamGrad<Ctx>::value)
-            for (int k = lane; k < dsim_par_words(nd, c.d.C); k += Exec::NL) c.pg[k] = 0.f;
+        dsim_par_zero<Exec::NL>(c, lane);
     });
     dsim_bwd_sweep<DsimSweepEntry<false, 0, false>>(c, ex, substeps, mm_freq, g_ckpt, g_lit);
     ex.run([&](int lane) {
@@ -4930,16 +4949,7 @@ DSIM_FN void dsim_sim_step_backward(const Ctx& c, Exec& ex, int substeps, int mm
         }
         if (g_gmact)
             for (int k = lane; k < M; k += Exec::NL) g_gmact[k] = WF(amact)[k];
-        if constexpr (DsimParamGrad<Ctx>::value) {
-            // per dof [5][nd] and per contact [C][4], summed over the substeps; written, every word by one lane
-            if (c.g_dof)
-                for (int it = lane; it < 5 * nd; it += Exec::NL) {
-                    const int j = it / nd, d = it - nd * j;
-                    c.g_dof[it] = c.pg[5 * d + j];
-                }
-            if (c.g_contact)
-                for (int k = lane; k < 4 * c.d.C; k += Exec::NL) c.g_contact[k] = c.pg[5 * nd + k];
-        }
+        dsim_par_store<Exec::NL>(c, lane, [](float x) __attribute__((always_inline)) { return x; });
     });
 }
 
@@ -5535,6 +5545,13 @@ DSIM_FN void dsim_env_fused_backward(const Ctx& c, Exec& ex, const DsimEnvSpec& 
             for (int k = lane; k < nq; k += Exec::NL) g_gq_in[k] = 0.f;
             for (int k = lane; k < nd; k += Exec::NL) g_gqd_in[k] = 0.f;
             for (int k = lane; k < sp.n_act; k += Exec::NL) g_gactions[k] = 0.f;
+            if constexpr (DsimParamGrad<Ctx>::value) {
+                // (outputs are written, never accumulated: the caller's buffers may be uninitialised)
+                if (c.g_dof)
+                    for (int k = lane; k < 5 * nd; k += Exec::NL) c.g_dof[k] = 0.f;
+                if (c.g_contact)
+                    for (int k = lane; k < 4 * c.d.C; k += Exec::NL) c.g_contact[k] = 0.f;
+            }
         });
         return;
     }
@@ -5601,6 +5618,7 @@ DSIM_FN void dsim_env_fused_backward(const Ctx& c, Exec& ex, const DsimEnvSpec& 
             WF(aact)[k] = 0.f;
         });
         for (int k = lane; k < M; k += Exec::NL) WF(amact)[k] = 0.f;
+        dsim_par_zero<Exec::NL>(c, lane);
     });
     dsim_env_load_actions(c, ex, sp, g_actions, true);
     dsim_env_observe_adjoint(c, ex, sp, g_gobs, g_grew, g_gobs_before, ep_flags, true);
@@ -5632,6 +5650,8 @@ DSIM_FN void dsim_env_fused_backward(const Ctx& c, Exec& ex, const DsimEnvSpec& 
             else g += sc * WF(aact)[sp.act_offset + k];
             g_gactions[k] = (a >= -1.0f && a <= 1.0f) ? clean(g) : 0.f;
         });
+        // (the parameter outputs under the same scrub: an extension of the reference's hooks, include/dsim.h)
+        dsim_par_store<Exec::NL>(c, lane, clean);
     });
 }
 

@@ -1000,6 +1000,32 @@ __global__ __launch_bounds__((DSIM_NL * NW * (MODE == 1 ? 2 : 1)), DSIM_WIDE_WAV
                             gq_in + e * nq, gqd_in + e * nd, gactions + (size_t)e * sp.n_act);
 }
 
+// dsim_env_step_backward_params: the fused env adjoint of dsim_env_bwd_kernel (plain launch mode: the same bits) on DsimParCtxT,
+// as dsim_bwd_param_kernel is the step adjoint on it: the same accumulator words behind the adjoint image, the same outputs.
+struct DsimEnvParArgs {
+    const float *ckpt, *actions, *gq_out, *gqd_out, *gobs, *grew, *gobs_before;   // cotangent inputs may be null (= zeros)
+    float *gq_in, *gqd_in, *gactions;
+    float *g_dof, *g_contact;   // [n_envs][5][nd], [n_envs][C][4]; either may be null
+};
+template <class O, class D, int NW, bool LEAN>
+__global__ __launch_bounds__((DSIM_NL * NW), DSIM_WIDE_WAVES(NW)) void dsim_env_bwd_param_kernel(KCommonT<O, D> k, DsimEnvSpec sp, DsimEnvParArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int e = (int)blockIdx.x;
+    if (e >= k.n_envs) return;
+    DevExec<NW, dsim_pf_regs<O, NW, LEAN, DSIM_MODE_PLAIN>(), dsim_const_words<O>(), false, 1> ex;
+    DsimParCtxT<O, D, LEAN> c;
+    static_cast<DsimCtxT<O, D, LEAN>&>(c) = start_env<LEAN, DSIM_MODE_PLAIN>(lds, k, k.o.total_words, ex, e);
+    const size_t nq = k.d.nq, nd = k.d.nd, C = k.d.C;
+    c.pg = lds + k.o.total_words;
+    c.g_dof = a.g_dof ? a.g_dof + e * 5 * nd : nullptr;
+    c.g_contact = (a.g_contact && C) ? a.g_contact + e * 4 * C : nullptr;
+    dsim_env_fused_backward(c, ex, sp, k.substeps, k.mm_freq, a.ckpt + (size_t)e * k.ckpt_stride,
+                            a.actions + (size_t)e * sp.n_act, a.gq_out ? a.gq_out + e * nq : nullptr,
+                            a.gqd_out ? a.gqd_out + e * nd : nullptr, a.gobs ? a.gobs + (size_t)e * sp.n_obs : nullptr,
+                            a.grew ? a.grew + e : nullptr, a.gobs_before ? a.gobs_before + (size_t)e * sp.n_obs : nullptr,
+                            a.gq_in + e * nq, a.gqd_in + e * nd, a.gactions + (size_t)e * sp.n_act);
+}
+
 template <class O, class D, int NW>
 __global__ __launch_bounds__(DSIM_NL * NW) void dsim_env_obs_kernel(KCommonT<O, D> k, DsimEnvSpec sp,
                                                                const float* __restrict__ q,
@@ -1447,13 +1473,16 @@ template <class Fam, class... Listed> constexpr bool dsim_readout_listed(std::tu
 }
 
 // f(kernel) for every kernel of a model outside the step families: the read-outs above, the multi-cotangent sweep and the
-// parameter-gradient sweep (full and lean checkpoints; step_backward_multi and dsim_step_backward_params launch them).
+// parameter-gradient sweeps of the step and of the fused env step (full and lean checkpoints; step_backward_multi,
+// dsim_step_backward_params and dsim_env_step_backward_params launch them).
 template <class O, class D, int NW, class F, class... Listed> void for_each_readout_kernel(F&& f, std::tuple<Listed...>*) {
     (f(reinterpret_cast<const void*>(Listed::template kernel<O, D, NW>())), ...);
     f(reinterpret_cast<const void*>(&dsim_bwd_multi_kernel<O, D, NW, false>));
     f(reinterpret_cast<const void*>(&dsim_bwd_multi_kernel<O, D, NW, true>));
     f(reinterpret_cast<const void*>(&dsim_bwd_param_kernel<O, D, NW, false>));
     f(reinterpret_cast<const void*>(&dsim_bwd_param_kernel<O, D, NW, true>));
+    f(reinterpret_cast<const void*>(&dsim_env_bwd_param_kernel<O, D, NW, false>));
+    f(reinterpret_cast<const void*>(&dsim_env_bwd_param_kernel<O, D, NW, true>));
 }
 template <class O, class D, int NW, class F> void for_each_readout_kernel(F&& f) {
     for_each_readout_kernel<O, D, NW>(f, static_cast<dsim_readout_families*>(nullptr));
@@ -1926,6 +1955,31 @@ int dsim_env_step_backward(const dsim_model* m, const dsim_env_spec* env, int n_
     if (!ckpt || !actions || !gq_in || !gqd_in || !gactions) return fail(DSIM_ERR_INVALID, "null pointer");
     return launch_step<dsim_env_bwd_kernel_family>(m, n_envs, dt, substeps, mm_freq, hip_stream, sp, ckpt, actions, gq_out, gqd_out,
                                                    gobs, grew, gobs_before_reset, gq_in, gqd_in, gactions);
+}
+
+int dsim_env_step_backward_params(const dsim_model* m, const dsim_env_spec* env, int n_envs, const float* ckpt,
+                                  const float* actions, float dt, int substeps, int mm_freq, const float* gq_out,
+                                  const float* gqd_out, const float* gobs, const float* grew, const float* gobs_before_reset,
+                                  float* gq_in, float* gqd_in, float* gactions, float* g_dof, float* g_contact, void* hip_stream) {
+    int rc = check_common(m, n_envs, dt, substeps, mm_freq);
+    if (rc) return rc;
+    DsimEnvSpec sp;
+    rc = make_spec(m, env, sp);
+    if (rc) return rc;
+    if (!ckpt || !actions || !gq_in || !gqd_in || !gactions) return fail(DSIM_ERR_INVALID, "null pointer");
+    const size_t bytes = ((size_t)m->lay.o.total_words + (size_t)(5 * m->lay.d.nd + 4 * m->lay.d.C)) * 4;   // + dsim_par_words(nd, C)
+    if (bytes > 160 * 1024) return fail(DSIM_ERR_LIMIT, "model needs more than 160 KiB of LDS per environment with the parameter accumulators");
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    return dispatch(m, [&](auto o, auto d, auto nw) {
+        using O = decltype(o);
+        using D = decltype(d);
+        constexpr int NW = decltype(nw)::value;
+        auto k = make_k(m, o, d, n_envs, dt, substeps, mm_freq);
+        const DsimEnvParArgs a{ckpt, actions, gq_out, gqd_out, gobs, grew, gobs_before_reset, gq_in, gqd_in, gactions, g_dof, g_contact};
+        if (m->lean) hipLaunchKernelGGL((dsim_env_bwd_param_kernel<O, D, NW, true>), dim3(n_envs), dim3(DSIM_NL * NW), bytes, st, k, sp, a);
+        else hipLaunchKernelGGL((dsim_env_bwd_param_kernel<O, D, NW, false>), dim3(n_envs), dim3(DSIM_NL * NW), bytes, st, k, sp, a);
+        return launched("launch dsim_env_bwd_param_kernel");
+    });
 }
 
 int dsim_env_observe(const dsim_model* m, const dsim_env_spec* env, int n_envs, const float* q, const float* qd,

@@ -66,6 +66,11 @@ READOUTS = {r.name: r for r in (
 class Engine:
     """Owns the device copy of one articulation template on one GPU."""
 
+    # Parameter epoch: a Python int that set_params, set_env_params, reserve_env_params and reset_params each bump.  EnvStepParams
+    # records it in forward and refuses a backward under another one: the checkpoint would be consumed under other values than
+    # its forward ran with.
+    param_epoch = 0
+
     def __init__(self, template: ArticulationTemplate, device, ckpt_mode=None, specialise=None):
         """ckpt_mode: "full" (default; $DIFFRL_AMD_CKPT overrides) -- the forward launch streams every intermediate the
         adjoint reads to HBM -- or "lean" -- (q, qd) per substep only, the adjoint recomputes (include/dsim.h).
@@ -442,6 +447,7 @@ class Engine:
         for a reservation only when the number of environments changes."""
         self._call(self._lib.dsim_model_reserve_env_params, self._h, int(n_envs))
         self._env_rows = int(n_envs)
+        self.param_epoch += 1
 
     def set_env_params(self, p):
         """dsim_model_set_env_params for every field of p (an EnvStepParameters, or its six tensors in that order; an entry may
@@ -468,6 +474,7 @@ class Engine:
                 self._arg(x, n * size, name)
         if getattr(self, "_env_rows", 0) != n:
             self.reserve_env_params(n)
+        self.param_epoch += 1
         for field, (x, size) in enumerate(zip(ts, sizes)):
             if x is not None and size:
                 self._call(self._lib.dsim_model_set_env_params, self._h, field, n, _ptr(x))
@@ -485,6 +492,7 @@ class Engine:
         for x, size, name in zip(ts, sizes, StepParameters.FIELDS):   # (all of them before the first copy: all are set or none)
             if x is not None:
                 self._arg(x, size, name)
+        self.param_epoch += 1
         for field, (x, size) in enumerate(zip(ts, sizes)):
             if x is not None and size:
                 self._call(self._lib.dsim_model_set_params, self._h, field, _ptr(x))
@@ -495,7 +503,7 @@ class Engine:
             self._params0 = self.step_parameters()
         if getattr(self, "_env_rows", 0):
             self.reserve_env_params(0)
-        self.set_params(self._params0)
+        self.set_params(self._params0)   # (bumps the parameter epoch)
 
     def _fold_index(self):
         """(link of every dof [nd], the hinge / slider dofs [k], their coordinates [k]) on the device"""
@@ -587,6 +595,33 @@ class Engine:
                    substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gobs), _ptr(grew), _ptr(gobs_before), _ptr(gq), _ptr(gqd),
                    _ptr(ga))
         return gq, gqd, ga
+
+    def env_backward_params(self, spec, ckpt, actions, dt, substeps, mm_freq, gq_out, gqd_out, gobs, grew, gobs_before=None,
+                            want_dof=True, want_contact=True):
+        """dsim_env_step_backward_params -> (gq, gqd, ga, g_dof [n_envs, 5, n_qd] | None, g_contact [n_envs, C, 4] | None): the
+        gradients of env_backward, bit for bit, and per environment the parameter terms backward_params returns, summed over the
+        substeps of this step.  Any cotangent may be None (= zeros).  The checkpoint is consumed under the parameter values its
+        forward ran with; one launch, plain launch mode."""
+        n = self._check_ckpt(ckpt, substeps, mm_freq)
+        self._arg(actions, n * spec.n_act, "actions")
+        for g, width, name in ((gq_out, self.n_q, "gq_out"), (gqd_out, self.n_qd, "gqd_out"), (gobs, spec.n_obs, "gobs"),
+                               (grew, 1, "grew"), (gobs_before, spec.n_obs, "gobs_before_reset")):
+            if g is not None:
+                self._arg(g, n * width, name)
+        Cn = self.template.n_contacts
+        gq = self._new(n * self.n_q)
+        gqd = self._new(n * self.n_qd)
+        ga = self._new(n, spec.n_act)
+        g_dof = self._new(n, 5, self.n_qd) if want_dof else None
+        g_con = (self._new(n, Cn, 4) if Cn else torch.zeros(n, 0, 4, device=self.device)) if want_contact else None
+        for g, numel, name in ((gq, n * self.n_q, "gq_in"), (gqd, n * self.n_qd, "gqd_in"), (ga, n * spec.n_act, "gactions"),
+                               (g_dof, n * 5 * self.n_qd, "g_dof"), (g_con, n * Cn * 4, "g_contact")):
+            if g is not None:
+                self._arg(g, numel, name)
+        self._call(self._lib.dsim_env_step_backward_params, self._h, C.byref(spec), n, _ptr(ckpt), _ptr(actions), C.c_float(dt),
+                   substeps, mm_freq, _ptr(gq_out), _ptr(gqd_out), _ptr(gobs), _ptr(grew), _ptr(gobs_before), _ptr(gq), _ptr(gqd),
+                   _ptr(ga), _ptr(g_dof), _ptr(g_con))
+        return gq, gqd, ga, g_dof, g_con
 
     def env_observe(self, spec, q, qd, stored_actions):
         n = self._state(q, (qd, self.n_qd, "qd"), (stored_actions, spec.n_act, "stored_actions"))
@@ -759,6 +794,55 @@ class EnvStep(torch.autograd.Function):
         gq, gqd, ga = ctx.engine.env_backward(ctx.spec, ckpt, actions, ctx.dt, ctx.substeps, ctx.mm_freq, c(gq_out),
                                               c(gqd_out), c(gobs), c(grew), c(gobs_before))
         return None, None, None, None, None, None, gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), ga.view(ctx.shapes[2])
+
+
+class EnvStepParams(torch.autograd.Function):
+    """EnvStep with the six tensors of a StepParameters (per_env False) or an EnvStepParameters (per_env True) as inputs:
+    (joint_q, joint_qd, actions, six parameter tensors) -> EnvStep's outputs, and a gradient for every parameter tensor that
+    requires one.  forward does NOT set the values on the model (that would be six copies per step of a rollout): the caller has
+    set them (DFlexEnv.set_step_parameters) and forward records the Engine's parameter epoch.  backward raises DsimError if the
+    epoch moved -- the checkpoint would be consumed under other values than its forward ran with --, launches
+    dsim_env_step_backward_params with only the outputs needed and folds them (Engine.fold_param_grads): summed over the
+    environments for shared parameters, row e for environment e otherwise.  Autograd sums the steps of a rollout."""
+
+    @staticmethod
+    def forward(ctx, engine, spec, episode, dt, substeps, mm_freq, per_env, q, qd, actions, *params):
+        if len(params) != 6:
+            raise capi.DsimError("EnvStepParams takes the six tensors of a StepParameters / EnvStepParameters")
+        ctx.epoch, ctx.per_env = engine.param_epoch, bool(per_env)
+        ctx.param_shapes = tuple(p.shape for p in params)
+        q, qd, actions = q.contiguous(), qd.contiguous(), actions.contiguous()
+        out = engine.env_forward(spec, q.detach(), qd.detach(), actions.detach(), dt, substeps, mm_freq, True, episode)
+        q_out, qd_out, obs, rew, ckpt = out[:5]
+        ctx.engine, ctx.spec, ctx.dt, ctx.substeps, ctx.mm_freq = engine, spec, dt, substeps, mm_freq
+        ctx.shapes = (q.shape, qd.shape, actions.shape)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(ckpt, actions.detach())
+        res = (q_out.view(q.shape), qd_out.view(qd.shape), obs, rew)
+        if episode is not None:
+            obs_before, done = out[5], out[6]
+            ctx.mark_non_differentiable(done)
+            res = res + ((obs_before if obs_before is not None else obs.new_empty(0)), done)
+        return res
+
+    @staticmethod
+    def backward(ctx, gq_out, gqd_out, gobs, grew, gobs_before=None, gdone=None):
+        e = ctx.engine
+        if e.param_epoch != ctx.epoch:
+            raise capi.DsimError("the model's parameters were set again between this env.step() and its backward (parameter epoch "
+                                 "%d -> %d): the checkpoint would be consumed under other values than its forward ran with"
+                                 % (ctx.epoch, e.param_epoch))
+        ckpt, actions = ctx.saved_tensors
+        c = lambda g: g.contiguous() if g is not None else None  # noqa: E731
+        if gobs_before is not None and gobs_before.numel() == 0:
+            gobs_before = None
+        need = ctx.needs_input_grad[10:]
+        gq, gqd, ga, g_dof, g_con = e.env_backward_params(ctx.spec, ckpt, actions, ctx.dt, ctx.substeps, ctx.mm_freq, c(gq_out),
+                                                          c(gqd_out), c(gobs), c(grew), c(gobs_before), want_dof=any(need[:5]),
+                                                          want_contact=need[5])
+        gp = [g.view(s) if g is not None else None
+              for g, s in zip(e.fold_param_grads(g_dof, g_con, need, per_env=ctx.per_env), ctx.param_shapes)]
+        return (None,) * 7 + (gq.view(ctx.shapes[0]), gqd.view(ctx.shapes[1]), ga.view(ctx.shapes[2]), *gp)
 
 
 class ReadoutFunction(torch.autograd.Function):

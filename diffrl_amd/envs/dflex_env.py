@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import dflex as df
-from ..engine import EnvStep
+from ..engine import EnvStep, EnvStepParameters, EnvStepParams
 
 ASSET_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
 
@@ -50,6 +50,8 @@ class DFlexEnv:
     sanitize_grads = False   # nan_to_num hooks on the state / action gradients (humanoid.py:195-206)
     keep_act_on_clear = False
     fused = os.environ.get("DIFFRL_AMD_UNFUSED", "0") != "1"   # one launch per env.step
+    step_params = None       # the StepParameters / EnvStepParameters in force (set_step_parameters, randomize_step_parameters)
+    _step_params_stamp = None
 
     def __init__(self, num_envs, num_obs, num_act, episode_length, MM_caching_frequency=1, seed=0, no_grad=True,
                  render=False, device="cuda:0"):
@@ -137,9 +139,10 @@ class DFlexEnv:
         that device) and multiplies the whole array.  -> the engine.EnvStepParameters that were set.  Call it outside a graph
         capture (it allocates; the first call reserves the model's per-environment block); to draw again between captured steps,
         update tensors in place and hand them to model.engine().set_env_params, which is capturable from then on.  The values
-        are not redrawn when an environment restarts inside the fused step, and the fused env adjoint returns no parameter
-        gradients (those are the integrator's: SemiImplicitIntegrator.forward(..., params=...)).  model.engine().reset_params()
-        goes back to the template's values for all environments."""
+        are not redrawn when an environment restarts inside the fused step.  The tensors returned are env.step_params: set
+        requires_grad on one of them and env.step() returns its gradient, row e from environment e (set_step_parameters has
+        the details; after an in-place update call set_step_parameters(p) again).  set_step_parameters(None) goes back to the
+        template's values for all environments."""
         eng = self.model.engine()
         p = eng.env_step_parameters(self.num_envs)
         n, dev = self.num_envs, p.joint_target_ke.device
@@ -160,7 +163,38 @@ class DFlexEnv:
             else:
                 x *= factor(rng).view(n, 1)
         eng.set_env_params(p)
+        self._keep_step_params(eng, p)
+        return p
+
+    def _keep_step_params(self, eng, p):
+        """p as env.step_params, with what its values on the model are known by: the Engine's parameter epoch and the in-place
+        version counter of every tensor (host-side integers: no device work)"""
         self.step_params = p
+        self._step_params_stamp = None if p is None else (eng.param_epoch, tuple(t._version for t in p.tensors()))
+
+    def set_step_parameters(self, p):
+        """Puts the values of p -- an engine.StepParameters (shared by all environments) or engine.EnvStepParameters (row e for
+        environment e) -- on the model (Engine.set_params / set_env_params) and keeps p as env.step_params; None: back to the
+        template's values (Engine.reset_params) and the plain path.  Every later env.step() runs under these values.  While
+        gradients are on and a tensor of p requires grad, env.step() also differentiates with respect to p: one launch each way
+        as before (the adjoint is dsim_env_step_backward_params), a shared tensor receives the sum over the environments, a
+        per-environment tensor row e from environment e, and autograd sums the steps of a rollout.
+        The values are COPIED here, not read at every step: after changing a tensor of p (an optimiser step) call this again
+        before the next env.step(), and not between a step and its backward -- that backward raises DsimError (the checkpoint
+        would be consumed under other values than its forward ran with).  A differentiating env.step() checks that the model
+        still holds what was copied and raises DsimError otherwise: after a tensor of p was changed in place, or after the
+        Engine's values were set behind the environment (engine.set_params / set_env_params / reset_params).  Capturable, with one exception: the first call with
+        an EnvStepParameters of a new number of environments allocates the model's per-environment block, and None releases
+        it.  Under a GraphedRollout make that first call before the capture and call set_step_parameters(p) first in the body,
+        so that a replay sees in-place updates of its leaves, the tensors of p."""
+        eng = self.model.engine()
+        if p is None:
+            eng.reset_params()
+        elif isinstance(p, EnvStepParameters):
+            eng.set_env_params(p)
+        else:
+            eng.set_params(p)
+        self._keep_step_params(eng, p)
         return p
 
     def stored_actions(self, actions):
@@ -279,6 +313,16 @@ class DFlexEnv:
                                                               float(self.sim_dt), self.sim_substeps,
                                                               self.MM_caching_frequency, False, epi)
             obs_before = None
+        elif self.step_params is not None and any(t.requires_grad for t in self.step_params.tensors()):
+            p = self.step_params
+            if (eng.param_epoch, tuple(t._version for t in p.tensors())) != self._step_params_stamp:
+                from ..capi import DsimError
+                raise DsimError("%s.step: the model no longer holds the values of env.step_params (a tensor was changed in place, "
+                                "or the Engine's parameters were set directly): the gradient would be taken at other values; "
+                                "call env.set_step_parameters(p) again first" % type(self).__name__)
+            q, qd, obs, rew, obs_before, done = EnvStepParams.apply(eng, spec, epi, float(self.sim_dt), self.sim_substeps,
+                                                                    self.MM_caching_frequency, isinstance(p, EnvStepParameters),
+                                                                    self.state.joint_q, self.state.joint_qd, actions, *p.tensors())
         else:
             q, qd, obs, rew, obs_before, done = EnvStep.apply(eng, spec, epi, float(self.sim_dt), self.sim_substeps,
                                                               self.MM_caching_frequency, self.state.joint_q,

@@ -318,8 +318,8 @@ int dsim_model_set_env_params(dsim_model* m, int field, int n_envs, const float*
  *                           substeps (eval_rigid_contacts_art, sim.py:1137-1206): zeros for a contact that does not penetrate;
  *                           kf only in the kf |vt| < -mu c ke friction branch, mu only in the other.  Not touched when C == 0.
  * The checkpoint is consumed in the mode it was written in AND under the parameter values the forward call ran with: set the
- * same values again (dsim_model_set_params) if they were changed in between.  There is no literal, multi-cotangent or fused-env
- * variant of this call. */
+ * same values again (dsim_model_set_params) if they were changed in between.  There is no literal or multi-cotangent variant of
+ * this call; the fused env step has dsim_env_step_backward_params below. */
 int dsim_step_backward_params(const dsim_model* m, int n_envs,
                               const float* ckpt, const float* act, const float* muscle_act,
                               float dt, int substeps, int mm_freq,
@@ -517,6 +517,29 @@ int dsim_env_step_backward(const dsim_model* m, const dsim_env_spec* env, int n_
                            const float* gq_out, const float* gqd_out, const float* gobs, const float* grew,
                            const float* gobs_before_reset,
                            float* gq_in, float* gqd_in, float* gactions, void* hip_stream);
+
+/* dsim_env_step_backward with the parameter gradients of dsim_step_backward_params: the same arguments in the same order, then
+ * g_dof [N][5][n_qd] and g_contact [N][C][4] with the layout and the per-item terms documented there -- summed over the substeps
+ * of this step, per environment, WRITTEN (callers may hand in uninitialised buffers), no atomics.  Either may be NULL; with both
+ * NULL the call is the fused adjoint in the plain launch mode.  gq_in, gqd_in and gactions equal dsim_env_step_backward's BIT FOR
+ * BIT (one kernel family more, one environment per workgroup, plain launch mode only).
+ *   - The cotangents of the reward, the observation and obs_before_reset reach the parameters through the state they are
+ *     functions of, so an environment the forward step restarted keeps the parameter terms of its reward and obs_before_reset
+ *     cotangents (gq_out / gqd_out / gobs are ignored for it, as above).
+ *   - An environment whose step ended invalid (the case in which dsim_env_step_backward returns zeros) gets zero rows.
+ *   - With sanitize_grads set, g_dof and g_contact go through the same scrub as the three state cotangents.  A DELIBERATE
+ *     EXTENSION: the reference's nan_to_num hooks sit on joint_q / joint_qd / actions only and do not cover model tensors, where
+ *     one NaN would poison the parameter gradient of the whole rollout.
+ * Same LDS limit (DSIM_ERR_LIMIT with the accumulators counted) and the same rule on parameter values as
+ * dsim_step_backward_params: the checkpoint is consumed under the values the forward call ran with; in per-environment mode
+ * n_envs may not exceed the reserved rows.  Capturable, no host synchronisation. */
+int dsim_env_step_backward_params(const dsim_model* m, const dsim_env_spec* env, int n_envs,
+                                  const float* ckpt, const float* actions,
+                                  float dt, int substeps, int mm_freq,
+                                  const float* gq_out, const float* gqd_out, const float* gobs, const float* grew,
+                                  const float* gobs_before_reset,
+                                  float* gq_in, float* gqd_in, float* gactions,
+                                  float* g_dof, float* g_contact, void* hip_stream);
 
 /* observation + reward of a given state with given stored actions (reset / initialize_trajectory path) */
 int dsim_env_observe(const dsim_model* m, const dsim_env_spec* env, int n_envs, const float* q, const float* qd,
