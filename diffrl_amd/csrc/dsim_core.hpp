@@ -1529,7 +1529,53 @@ template <class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics_walk_mid(const
 // component each, or one link per lane.  All loads first, no store before the end of the walk; every lane runs the whole block
 // with the same sequence of cross-lane operations (positions a chain does not have are identities, not skipped), and the
 // phase's interface is the one-link-per-lane form's: same words of xsc, v, a, i10, f, S.
-template <class Ctx, class Exec, class B> DSIM_FN void dsim_fk_quad_block(const Ctx& c, Exec& ex, const B& b, const DsimTopoRegs& tp) {
+// ---- launch-invariant operands of that block in registers -----------------------------------------------------------------------
+// The block reloaded, in every substep and behind per-lane addresses, the constants of the lane's link and of its chain: the
+// joint-frame translations and axes of the chain positions, the centre of mass, gravity, the six inertia words and the mass
+// (14 words for a tree three levels deep).  Nothing inside a launch writes them after the prologue.  An executor with a bregs()
+// block keeps them per lane across the substeps of a forward launch (dsim_body_regs_begin, in front of the substep loop: no
+// flags inside the loop); the four-lanes-per-link layout only, where every word is one float per lane.  Same words, same
+// operations: no rounding changes.  Executors without the block (the host harness), the one-link-per-lane backend (two
+// environments per wavefront) and every caller outside the substep loop (read-outs, the adjoint's recomputation) reload.
+struct DsimBodyRegs {
+    float ppj[DSIM_QUAD_DEPTH], ax[DSIM_QUAD_DEPTH];
+    float com, grav, ic[6], m;
+};
+template <class Exec, class = void> struct DsimHasBodyRegs : std::false_type {};
+template <class Exec> struct DsimHasBodyRegs<Exec, std::void_t<decltype(std::declval<Exec&>().bregs(0))>> : std::true_type {};
+template <class Ctx, class Exec> struct DsimBodyRegsFwd {
+    static constexpr bool value = DsimHasBodyRegs<Exec>::value && DsimQuadKin<Ctx, Exec::NL>::QUAD;
+};
+// the loads themselves: what dsim_fk_quad_block fetches where it has no register block (same addresses, same words)
+template <class Ctx, class B> DSIM_FN void dsim_body_regs_load(const Ctx& c, const B& b, const DsimTopoRegs& tp, DsimBodyRegs& br) {
+    using D = decltype(c.d);
+    const int i = tp.qk_i;
+    br.ppj[0] = b.template ld<3>(CF(xpj) + 7 * tp.qk_link[0]);
+#pragma unroll
+    for (int p = 1; p < D::D; ++p) {
+        br.ppj[p] = b.template ld<3>(CF(xpj) + 7 * tp.qk_link[p]);
+        br.ax[p] = b.template ld<3>(CF(axis) + 3 * tp.qk_link[p]);
+    }
+    br.com = b.template ld<3>(CF(com) + 3 * i);
+    br.grav = b.template ld<3>(CF(grav));
+    const float* icp = CF(ic6) + 6 * i;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) br.ic[k] = icp[k];
+    br.m = CF(mass)[i];
+}
+// The forward launches call this once, behind the prologue (constant image landed, topology records set) and in front of the
+// substep loop, next to dsim_joint_regs_begin.
+template <class Ctx, class Exec> DSIM_FN void dsim_body_regs_begin(const Ctx& c, Exec& ex) {
+    if constexpr (DsimBodyRegsFwd<Ctx, Exec>::value) {
+        ex.run([&](int lane) {
+            const DsimTopoRegs& tp = ex.topo(lane);
+            const DsimQuadLanes<Exec> b(ex, lane, tp.qc);
+            dsim_body_regs_load(c, b, tp, ex.bregs(lane));
+        });
+    }
+}
+// BREGS: the caller is a substep of a launch that has called dsim_body_regs_begin (dsim_fwd_substep)
+template <bool BREGS, class Ctx, class Exec, class B> DSIM_FN void dsim_fk_quad_block(const Ctx& c, Exec& ex, const B& b, const DsimTopoRegs& tp) {
     using D = decltype(c.d);
     typedef typename B::T T;
     typedef DsimQuadSv<B> SV;
@@ -1545,18 +1591,38 @@ template <class Ctx, class Exec, class B> DSIM_FN void dsim_fk_quad_block(const 
     v.v = b.template ld<3>(qd + tp.qk_ds[0] + 3);
     T ppj[D::D], ax[D::D];
     float ang[D::D], rate[D::D];
-    ppj[0] = b.template ld<3>(CF(xpj) + 7 * tp.qk_link[0]);
+    T com, grav;
+    float ic0, ic1, ic2, ic3, ic4, ic5, m;
+    constexpr bool REGS = BREGS && DsimBodyRegsFwd<Ctx, Exec>::value;
+    // (the reload path keeps the statement order it always had: the kernels that take it keep their opcode sequences)
+    if constexpr (!REGS) ppj[0] = b.template ld<3>(CF(xpj) + 7 * tp.qk_link[0]);
 #pragma unroll
     for (int p = 1; p < D::D; ++p) {
-        ppj[p] = b.template ld<3>(CF(xpj) + 7 * tp.qk_link[p]);
-        ax[p] = b.template ld<3>(CF(axis) + 3 * tp.qk_link[p]);
+        if constexpr (!REGS) {
+            ppj[p] = b.template ld<3>(CF(xpj) + 7 * tp.qk_link[p]);
+            ax[p] = b.template ld<3>(CF(axis) + 3 * tp.qk_link[p]);
+        }
         ang[p] = q[tp.qk_cs[p]];
         rate[p] = qd[tp.qk_ds[p]];
     }
-    const T com = b.template ld<3>(CF(com) + 3 * i), grav = b.template ld<3>(CF(grav));
-    const float* icp = CF(ic6) + 6 * i;
-    const float ic0 = icp[0], ic1 = icp[1], ic2 = icp[2], ic3 = icp[3], ic4 = icp[4], ic5 = icp[5];
-    const float m = CF(mass)[i];
+    if constexpr (REGS) {
+        const DsimBodyRegs& br = ex.bregs(b.lane);
+        ppj[0] = br.ppj[0];
+#pragma unroll
+        for (int p = 1; p < D::D; ++p) {
+            ppj[p] = br.ppj[p];
+            ax[p] = br.ax[p];
+        }
+        com = br.com; grav = br.grav;
+        ic0 = br.ic[0]; ic1 = br.ic[1]; ic2 = br.ic[2]; ic3 = br.ic[3]; ic4 = br.ic[4]; ic5 = br.ic[5];
+        m = br.m;
+    } else {
+        com = b.template ld<3>(CF(com) + 3 * i);
+        grav = b.template ld<3>(CF(grav));
+        const float* icp = CF(ic6) + 6 * i;
+        ic0 = icp[0]; ic1 = icp[1]; ic2 = icp[2]; ic3 = icp[3]; ic4 = icp[4]; ic5 = icp[5];
+        m = CF(mass)[i];
+    }
     // ---- root: free joint with an identity frame; v = v_j, a = 0
     T psp = b.add(qp, ppj[0]), rsp = qr;
     a.w = a.v = s0.w = s0.v = b.spl(0.f);
@@ -1634,17 +1700,17 @@ struct DsimContactPre {
     DsimContactConst cc;
     int body;
 };
-template <class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics_walk_quad(const Ctx& c, Exec& ex, float* g_row) {
+template <bool BREGS, class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics_walk_quad(const Ctx& c, Exec& ex, float* g_row) {
     using D = decltype(c.d);
     static_assert(DsimContactRegs<Ctx, Exec::NL>::value, "one contact per lane");
     dsim_fork_join_mid_pre(ex, [&](int lane) {
         const DsimTopoRegs& tp = ex.topo(lane);
         if constexpr (DsimQuadKin<Ctx, Exec::NL>::QUAD) {
             const DsimQuadLanes<Exec> b(ex, lane, tp.qc);
-            dsim_fk_quad_block(c, ex, b, tp);
+            dsim_fk_quad_block<BREGS>(c, ex, b, tp);
         } else {
             const DsimQuadScalar b;
-            dsim_fk_quad_block(c, ex, b, tp);
+            dsim_fk_quad_block<BREGS>(c, ex, b, tp);
         }
     }, [&](int lane) {
         // The quad block behind the hand-over is shorter than the contacts: the side block does everything that does not read
@@ -1667,7 +1733,8 @@ template <class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics_walk_quad(cons
 
 // g_row (one-phase dynamics only, DsimWaveDyn): the substep's checkpoint row -- its head (q, qd) is copied here, by the helper
 // wavefront where there is one, the rest beside the integrator (dsim_fwd_dynamics_wave)
-template <class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics(const Ctx& c, Exec& ex, float* g_row = nullptr) {
+// BREGS: called from the substep loop of a forward launch, behind dsim_body_regs_begin (DsimBodyRegs)
+template <bool BREGS = false, class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics(const Ctx& c, Exec& ex, float* g_row = nullptr) {
     ex.mark(1);
     if constexpr (DsimWideOverlap<Ctx, Exec>::value) {
         dsim_fwd_kinematics_wide(c, ex, g_row);
@@ -1678,7 +1745,7 @@ template <class Ctx, class Exec> DSIM_FN void dsim_fwd_kinematics(const Ctx& c, 
         return;
     }
     if constexpr (DsimQuadKin<Ctx, Exec::NL>::value) {
-        dsim_fwd_kinematics_walk_quad(c, ex, g_row);
+        dsim_fwd_kinematics_walk_quad<BREGS>(c, ex, g_row);
         return;
     }
     if constexpr (DsimContactsAfterWalk<Ctx, Exec::NL>::value) {
@@ -2862,11 +2929,12 @@ template <class Ctx, class Exec> DSIM_FN void dsim_check_unit_quats(const Ctx& c
 // one substep on the LDS-resident state; g_row / g_hinv: where to stream the saved block / the fresh inverse (or null).
 // A caller whose kernel takes DsimJointRegsFwd must have called dsim_joint_regs_begin behind the phase that stores act, and its
 // first substep must be a refresh substep (update_mass): the forward keeps no validity flags (the block's h_ok / c_ok are the
-// adjoint's), so a substep without both reads registers nobody loaded.  dsim_sim_step_forward and the env forward comply.
+// adjoint's), so a substep without both reads registers nobody loaded.  The same holds for dsim_body_regs_begin and the body
+// constants of the quad kinematics (DsimBodyRegsFwd).  dsim_sim_step_forward and the env forward comply.
 template <class Ctx, class Exec>
 DSIM_FN void dsim_fwd_substep(const Ctx& c, Exec& ex, bool update_mass, float* g_row = nullptr, float* g_hinv = nullptr) {
     constexpr bool wide = DsimWideOverlap<Ctx, Exec>::value;
-    dsim_fwd_kinematics(c, ex, (DsimWaveDyn<Ctx, Exec>::value || wide) ? g_row : nullptr);
+    dsim_fwd_kinematics<true>(c, ex, (DsimWaveDyn<Ctx, Exec>::value || wide) ? g_row : nullptr);
     dsim_fwd_external(c, ex);
     if constexpr (DsimWaveDyn<Ctx, Exec>::value) {
         if (update_mass) dsim_fwd_mass(c, ex);   // H depends on the kinematics only
@@ -2931,6 +2999,7 @@ DSIM_FN void dsim_sim_step_forward(const Ctx& c, Exec& ex, int substeps, int mm_
     });
     dsim_check_unit_quats(c, ex, g_status, env);
     dsim_joint_regs_begin(c, ex);
+    dsim_body_regs_begin(c, ex);
     for (int s = 0; s < substeps; ++s)
         dsim_fwd_substep(c, ex, (s % mm_freq) == 0, g_ckpt ? g_ckpt + (size_t)s * dsim_row(c) : nullptr,
                          g_ckpt ? dsim_ckpt_hinv(c, g_ckpt, substeps, s / mm_freq) : nullptr);
@@ -5382,6 +5451,7 @@ DSIM_FN void dsim_env_fused_forward(const Ctx& c, Exec& ex, const DsimEnvSpec& s
     dsim_env_load_actions(c, ex, sp, g_actions, true);
     dsim_check_unit_quats(c, ex, g_status, e);
     dsim_joint_regs_begin(c, ex);
+    dsim_body_regs_begin(c, ex);
     for (int s = 0; s < substeps; ++s)
         dsim_fwd_substep(c, ex, (s % mm_freq) == 0, g_ckpt ? g_ckpt + (size_t)s * dsim_row(c) : nullptr,
                          g_ckpt ? dsim_ckpt_hinv(c, g_ckpt, substeps, s / mm_freq) : nullptr);

@@ -566,6 +566,10 @@ template <int NW, int PF = 6, int CW = 0, bool HELPER = false, int EPW = 1> stru
     // false in every launch; kernels whose traits are off never touch the block and it costs them nothing.
     DsimJointRegs jregs_;
     __device__ __forceinline__ DsimJointRegs& jregs(int) { return jregs_; }
+    // ... and of what the quad kinematics would reload (dsim_core.hpp: DsimBodyRegs, DsimBodyRegsFwd): the constants of the lane's
+    // link and of its chain positions.  Loaded once per forward launch, in front of the substep loop; dead registers elsewhere.
+    DsimBodyRegs bregs_;
+    __device__ __forceinline__ DsimBodyRegs& bregs(int) { return bregs_; }
     // acc = fma(h[j], x of lane j of this lane's 16-lane ROW, acc) for j = 0 .. N - 1, from acc = 0: the mat-vec of the joint-space
     // phases (dof j on lane j, N <= 16: one row) as N v_fmac_f32 with the broadcast ON THE OPERAND (row_newbcast:j) instead of N
     // v_readlane + v_fmac pairs -- same terms, same order, same fused multiply-add.  x may have been written right before: the
